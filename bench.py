@@ -10,6 +10,10 @@ HBM when the clock starts.  `value` = frames that went through that chain per se
 rank owns its own sequences; the path shards by sequence, no data-path collective).  Rank 0 prints ONE JSON line.
 
   python bench.py --gpus N --steps K --warmup W          (starts its own N ranks when no launcher did)
+  python bench.py ... --full                             (+ the single-group pass, the secondary legs, the CPU baselines and parity spot checks)
+  python bench.py ... --dump-outputs DIR                 (what the last timed step handed back, as DIR/<name>.npy)
+
+A plain run sets up, warms up, times the K steps and prints the line; everything else the benchmark measures or checks runs under --full.
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
@@ -313,10 +317,12 @@ def tracking_leg(rank, local_rank, texture, steps, warmup, n_seq, n_groups, barr
         # every trajectory against the ground truth of the generator, every frame's tracked flag
         err, untracked, tracked_timed, overflowed = 0.0, 0, 0, 0
         tcw0 = st0 = obj0 = None
+        last = {"tcw": [], "stats": [], "objects": []}      # what the last timed step handed back, group after group (--dump-outputs)
         ob = {"detections": 0, "with_object": 0, "track_ok": 0, "max_abs_centre_error_m": 0.0, "reinit": 0, "dsd_tested": 0, "dsd_dynamic": 0}
         for g, t in enumerate(trks):
             tcw, st = t.fetch()
             untracked += int((st["tracked"] == 0).sum())
+            last["tcw"].append(tcw[-1]); last["stats"].append(st[-1])
             # a frame whose search windows overflowed the candidate store is not the reference's result: it does not count as tracked
             overflowed += int((st["overflowed"] != 0).sum())
             tracked_timed += int(((st["tracked"][warmup:] != 0) & (st["overflowed"][warmup:] == 0)).sum())
@@ -331,6 +337,7 @@ def tracking_leg(rank, local_rank, texture, steps, warmup, n_seq, n_groups, barr
                     err = max(err, float(np.abs(twc[ok, j] - truth[ok]).max()))
             if objects:
                 o = t.fetch_objects()
+                last["objects"].append(o[-1])
                 if g == 0:
                     obj0 = o
                 live = o["id"] >= 0
@@ -349,7 +356,7 @@ def tracking_leg(rank, local_rank, texture, steps, warmup, n_seq, n_groups, barr
                         for k, d in enumerate(q["dets"][i]):
                             if o[i, j, k]["track_ok"]:
                                 ob["max_abs_centre_error_m"] = max(ob["max_abs_centre_error_m"], float(np.abs(o[i, j, k]["tco"][:3] - d["pose7"][:3]).max()))
-        out.update(max_abs_position_error_m=err, untracked_frames=untracked, tracked_frames_timed=tracked_timed, overflowed_frames=overflowed, seqs=seqs, tcw_group0=tcw0, stats_group0=st0, obj_group0=obj0,
+        out.update(max_abs_position_error_m=err, untracked_frames=untracked, tracked_frames_timed=tracked_timed, overflowed_frames=overflowed, seqs=seqs, tcw_group0=tcw0, stats_group0=st0, obj_group0=obj0, last_step={k: np.concatenate(v) for k, v in last.items() if v},
                    objects=ob if objects else None)
     finally:       # a leg abandoned by an exception must not leave its arenas beside the next leg
         for t in trks:
@@ -1159,6 +1166,31 @@ def fp64_mfma_peak(local_rank):
     return v.value
 
 
+def _fields_as_float64(rec):
+    """a structured array as float64 [..., columns]: its fields in declaration order (vector fields spread out, `reserved` left out)"""
+    cols = []
+    for name in rec.dtype.names:
+        if name != "reserved":
+            cols.append(rec[name].astype(np.float64).reshape(rec.shape + (-1,)))
+    return np.concatenate(cols, -1)
+
+
+def dump_outputs(out_dir, last_step, rank=0):
+    """--dump-outputs: what the timed path handed back for its LAST step, every sequence of this GPU (group after group), one .npy per array:
+    tcw [S, 4, 4] float32 (zeros where a frame has no pose); frame_stats [S, 10] float64, the fields of ps_track_stat in the order of
+    tracker_device.STAT_DTYPE; with the object chain object_stats [S, max_objects, 25] float64, the fields of ps_object_stat in the order of
+    tracker_device.OBJECT_STAT_DTYPE (tco spread over 7 columns).  The sequences are generated from fixed seeds, so two runs with the same
+    arguments track the same inputs.  Ranks beyond the first write <name>_rank<r>.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"tcw": np.ascontiguousarray(last_step["tcw"], np.float32), "frame_stats": _fields_as_float64(last_step["stats"])}
+    if "objects" in last_step:
+        arrays["object_stats"] = _fields_as_float64(last_step["objects"])
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ("_rank%d" % rank if rank else "") + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 LINE_LIMIT = 8192             # the driver reads the bench line from a bounded tail of stdout: r04's 28.8 KB line came back unparsed
 
 
@@ -1274,7 +1306,7 @@ def emit(full):
     print(compact_line(full), flush=True)
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -1288,7 +1320,17 @@ def main():
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="only the headline loop")
     ap.add_argument("--no-alone", action="store_true", help="skip the single-group pass behind the timed region (profiling runs: the kernel trace then holds the timed loop only)")
-    args = ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="beside the headline loop: the single-group pass behind the timed region, the secondary legs, the CPU baselines and the "
+                                                        "parity spot checks (--no-alone / --no-secondary / --no-cpu take single parts out again); a plain run times the headline loop only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps: what the last one handed back (poses, frame and object records of every sequence) as DIR/<name>.npy")
+    args = ap.parse_args(argv)
+    if not args.full:
+        args.no_cpu = args.no_secondary = args.no_alone = True
+    return args
+
+
+def main():
+    args = parse_args()
 
     # `python bench.py --gpus N` with no launcher around it: this process only starts N ranks (fresh children, one per GPU)
     # and forwards rank 0's JSON line; it never touches the GPU itself.  PS_BENCH_LAUNCH_ONLY=1 (CPU test of this path):
@@ -1358,6 +1400,8 @@ def main():
     err = parallel.max_over_ranks(dist, head["max_abs_position_error_m"], RED_DEV)
     tracked_timed = parallel.sum_over_ranks(dist, head["tracked_frames_timed"], RED_DEV)
     overflowed = int(parallel.sum_over_ranks(dist, head["overflowed_frames"], RED_DEV))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, head["last_step"], rank)
 
     # the kernels of the step on their own: a short single-group pass over the same sequences (one stream: no overlap between kernels)
     alone = None

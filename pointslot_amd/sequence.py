@@ -150,7 +150,64 @@ def _sample(mips, u, v, footprint):
     return out
 
 
+_native = None
+
+
+def _native_lib():
+    """libps_seqrender.so (pointslot_amd/csrc/seq_render.cpp, built beside the HIP library): _render_numpy's per-pixel arithmetic as host C++,
+    same operations in the same order, same bits.  False when it has not been built (the numpy form then renders)."""
+    global _native
+    if _native is None:
+        import ctypes
+        p = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libps_seqrender.so")
+        try:
+            _native = ctypes.CDLL(p) if os.environ.get("PS_SEQ_NATIVE") != "0" and os.path.exists(p) else False
+        except OSError:
+            _native = False
+        if _native:
+            dp, ip, pp = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_void_p)
+            _native.ps_seq_render.restype = ctypes.c_int64
+            _native.ps_seq_render.argtypes = [dp, ctypes.c_double, ctypes.c_double, dp, ctypes.c_int, ctypes.c_int, pp, ip, ctypes.c_int, dp, ctypes.c_int, pp, ip,
+                                              ctypes.c_int, ctypes.c_double, dp, dp, ip]
+    return _native
+
+
+def _render_native(lib, cam_pos, yaw, K, w, h, mips, objs, texel_per_m):
+    """_render through libps_seqrender.so; None where a mip decision sits on a level boundary to within 1e-9 (another log2 could round the
+    other way: the caller renders that image with the numpy form)"""
+    import ctypes
+    dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)
+
+    def pack(chains):
+        arrs = [np.ascontiguousarray(t, np.float64) for ch in chains for t in ch]
+        ptrs = (ctypes.c_void_p * max(len(arrs), 1))(*[a.ctypes.data for a in arrs])
+        shapes = np.array([a.shape for a in arrs], np.int64).reshape(-1, 2)
+        return arrs, ptrs, shapes
+    m_keep, m_ptr, m_shape = pack([mips])
+    o_keep, o_ptr, o_shape = pack([o[5] for o in objs])
+    levels = {len(o[5]) for o in objs}
+    assert len(levels) <= 1
+    geo = np.array([o[:5] for o in objs], np.float64).reshape(-1, 5)
+    cam = np.ascontiguousarray(cam_pos, np.float64)
+    Kd = np.array(K, np.float64)
+    img = np.empty((h, w)); depth = np.empty((h, w)); oid = np.empty((h, w), np.int64)
+    unsure = lib.ps_seq_render(cam.ctypes.data_as(dp), float(np.cos(yaw)), float(np.sin(yaw)), Kd.ctypes.data_as(dp), w, h, m_ptr, m_shape.ctypes.data_as(ip), len(mips),
+                               geo.ctypes.data_as(dp), len(objs), o_ptr, o_shape.ctypes.data_as(ip), levels.pop() if levels else 0, float(texel_per_m),
+                               img.ctypes.data_as(dp), depth.ctypes.data_as(dp), oid.ctypes.data_as(ip))
+    return None if unsure else (img, depth, oid)
+
+
 def _render(cam_pos, yaw, K, w, h, mips, objs, texel_per_m=40.0):
+    """_render_numpy, through the host library where it is built (same bits, a small fraction of the time)"""
+    lib = _native_lib()
+    if lib:
+        out = _render_native(lib, cam_pos, yaw, K, w, h, mips, objs, texel_per_m)
+        if out is not None:
+            return out
+    return _render_numpy(cam_pos, yaw, K, w, h, mips, objs, texel_per_m)
+
+
+def _render_numpy(cam_pos, yaw, K, w, h, mips, objs, texel_per_m=40.0):
     """One pinhole view from cam_pos (world, y down) rotated by `yaw` about y.  Returns (image float, depth along the camera's z,
     object id per pixel (-1: static world)).  objs: list of (centre x, bottom y, z of the face, width, height, texture mips)."""
     fx, fy, cx, cy = K

@@ -94,6 +94,40 @@ def test_rendered_sequences_are_cached_and_read_back(tmp_path, monkeypatch):
     assert bench._seq_cache_path(("lateral", 2, 42, 0, "synthetic", 2)) != bench._seq_cache_path(job)
 
 
+def test_a_plain_run_is_the_headline_loop_only_and_full_brings_the_rest_back():
+    """Without --full nothing but the headline loop runs (no single-group pass, no secondary legs, no CPU baseline); --full is the whole
+    benchmark, from which the older switches still take single parts out."""
+    plain = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (plain.steps, plain.warmup, plain.full, plain.dump_outputs) == (7, 2, False, None)
+    assert plain.no_cpu and plain.no_secondary and plain.no_alone
+    full = bench.parse_args(["--full"])
+    assert full.full and not (full.no_cpu or full.no_secondary or full.no_alone)
+    part = bench.parse_args(["--full", "--no-cpu", "--dump-outputs", "somewhere"])
+    assert part.no_cpu and not part.no_secondary and not part.no_alone and part.dump_outputs == "somewhere"
+
+
+def test_dump_outputs_writes_float_arrays_of_the_last_step(tmp_path):
+    """--dump-outputs: the last step's poses and records as plain float .npy files, one row per sequence, the record fields as columns in the
+    order of the structures (without `reserved`)."""
+    import numpy as np
+    from pointslot_amd.tracker_device import OBJECT_STAT_DTYPE, STAT_DTYPE
+    S, K = 5, 3
+    st = np.zeros(S, STAT_DTYPE); st["tracked"] = 1; st["lm_inliers"] = np.arange(S); st["reserved"] = 77
+    ob = np.zeros((S, K), OBJECT_STAT_DTYPE); ob["id"] = -1; ob["tco"] = np.arange(7) + 0.5; ob["dyn_stereo"] = 2.25
+    tcw = np.tile(np.eye(4, dtype=np.float32), (S, 1, 1))
+    shapes = bench.dump_outputs(str(tmp_path / "out"), {"tcw": tcw, "stats": st, "objects": ob}, rank=0)
+    assert shapes == {"tcw": [S, 4, 4], "frame_stats": [S, 10], "object_stats": [S, K, 25]}
+    assert sorted(p.name for p in (tmp_path / "out").iterdir()) == ["frame_stats.npy", "object_stats.npy", "tcw.npy"]
+    a, f, o = (np.load(tmp_path / "out" / (n + ".npy")) for n in ("tcw", "frame_stats", "object_stats"))
+    assert a.dtype == np.float32 and f.dtype == np.float64 and o.dtype == np.float64
+    assert np.array_equal(a, tcw)
+    assert np.array_equal(f[:, 1], np.ones(S)) and np.array_equal(f[:, 8], np.arange(S)) and not (f == 77).any()
+    assert np.array_equal(o[..., 0], -np.ones((S, K))) and np.array_equal(o[0, 0, 16:23], np.arange(7) + 0.5) and (o[..., 24] == 2.25).all()
+    # the camera chain alone has no object records, a further rank writes beside the first
+    bench.dump_outputs(str(tmp_path / "out"), {"tcw": tcw, "stats": st}, rank=1)
+    assert sorted(p.name for p in (tmp_path / "out").iterdir()) == ["frame_stats.npy", "frame_stats_rank1.npy", "object_stats.npy", "tcw.npy", "tcw_rank1.npy"]
+
+
 def test_r06_line_carries_the_boundary_numbers_and_a_fraction_for_every_stage():
     """VERDICT r05 items 1 and 4, on the committed full result of the round (profiles/r06_bench_full.json): the compact line holds the one-sequence-
     per-GPU number of BASELINE configs[4] and the drop-in boundary's per-frame time with its split, `traffic` says where it comes from, and no stage

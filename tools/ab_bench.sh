@@ -1,12 +1,12 @@
 #!/bin/bash
-# developer tool: the headline loop alone (no secondary legs, no CPU baseline) once per library variant, same box, back to back.
+# developer tool: the headline loop and the single-group pass behind it (--full without secondary legs and CPU baseline) once per library variant, same box, back to back.
 # usage: tools/ab_bench.sh [-r repeats] <tag|default> ...    (build_exp/libps_<tag>.so from tools/build_variant.sh)
 R=2
 if [ "$1" = "-r" ]; then R=$2; shift 2; fi
 for rep in $(seq $R); do
 for v in "$@"; do
   if [ "$v" = default ]; then unset PS_LIB_PATH; else export PS_LIB_PATH=build_exp/libps_$v.so; fi
-  python3 bench.py --steps 20 --warmup 5 --no-secondary --no-cpu $AB_ARGS 2>/dev/null | tail -1 | python3 -c "
+  python3 bench.py --steps 20 --warmup 5 --full --no-secondary --no-cpu $AB_ARGS 2>/dev/null | tail -1 | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 ka=d.get('kernels_alone',{}).get('stage_ms_per_512_sequences',{})

@@ -7,5 +7,5 @@ ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 D=$ROOT/build_exp/csrc_$TAG
 rm -rf $D; mkdir -p $D
 cp $ROOT/pointslot_amd/csrc/*.hip $ROOT/pointslot_amd/csrc/*.h $ROOT/pointslot_amd/csrc/*.inc $ROOT/pointslot_amd/csrc/Makefile $D/
-make -C $D -j8 OUT=../libps_$TAG.so EXTRA="$*" > $D/build.log 2>&1 || { tail -20 $D/build.log; exit 1; }
+make -C $D -j8 ../libps_$TAG.so OUT=../libps_$TAG.so EXTRA="$*" > $D/build.log 2>&1 || { tail -20 $D/build.log; exit 1; }
 echo build_exp/libps_$TAG.so

@@ -3,7 +3,7 @@
 #
 #   gpurun --timeout 2400 -- 'tools/reproduce_profiles.sh r05'      ->  gpurun_out/profiles/r05_*   (copy into profiles/ and commit)
 #
-#   <round>_bench.json, <round>_bench_full.json      the driver's command (python3 bench.py --gpus 1 --steps 20 --warmup 5): line + full result (run LAST)
+#   <round>_bench.json, <round>_bench_full.json      the driver's command with every leg (python3 bench.py --gpus 1 --steps 20 --warmup 5 --full): line + full result (run LAST)
 #   <round>_unit_busy.json, _valu_busy.txt           vector ALU / scalar unit / LDS busy fractions per kernel (tools/valu_busy.sh)
 #   <round>_s1_chain.txt, _s1_chain_kernel_stats.csv one SLOT.MODE-4 sequence per handle, one frame in flight (BASELINE configs[4] per GPU)
 #   <round>_shim_path.txt, _shim_kernel_stats.csv, _shim_memory_copy_stats.csv   examples/stereo_kitti.cpp on the shim classes, host images
@@ -113,7 +113,7 @@ python3 -m pytest tests/test_track_device_gpu.py -m gpu -q -k config5_length > $
 
 # ---- 10. the driver's command, LAST: with this box's counter tables in profiles/ (bench.py reads its traffic / unit-busy figures there) ----
 for f in traffic valu_issue unit_busy legs_pmc; do [ -f $OUT/${ROUND}_$f.json ] && cp $OUT/${ROUND}_$f.json profiles/; done
-python3 bench.py --gpus 1 --steps $STEPS --warmup $WARM > $W/bench_line.txt 2> $W/bench_stderr.txt
+python3 bench.py --gpus 1 --steps $STEPS --warmup $WARM --full > $W/bench_line.txt 2> $W/bench_stderr.txt
 tail -1 $W/bench_line.txt > $OUT/${ROUND}_bench.json
 cp bench_full.json $OUT/${ROUND}_bench_full.json
 
