@@ -30,6 +30,7 @@ int main(int argc, char** argv) {
   ps_orb_enable_stage_timing(SLAM.leftExtractor().handle(), 1);
   ps_orb_enable_stage_timing(SLAM.rightExtractor().handle(), 1);
   std::cout << "Start processing sequence ... Images in the sequence: " << nImages << std::endl;
+  if (SLAM.usesDeviceFrames()) std::cout << "frame handles: on (the current frame is published once on the device and searched there)" << std::endl;
   for (int ni = 0; ni < nImages; ni++) {
     if (!LoadPGM(vstrImageLeft[ni], imLeft, w, h) || !LoadPGM(vstrImageRight[ni], imRight, wr, hr) || wr != w || hr != h) {
       std::cerr << "Failed to load image at: " << vstrImageLeft[ni] << std::endl;

@@ -327,6 +327,57 @@ typedef struct ps_fuse_problem {
 } ps_fuse_problem;
 int ps_fuse_search(ps_matcher* m, ps_fuse_problem* problems, int nproblems);
 
+/* ------------------------------------------------------------------------------------------------
+ * Frame handle — "this frame is already on the device".  A stereo Frame's search-relevant state, kept in HBM between the calls
+ * that search into it: what Frame::Frame leaves in mvKeysUn, mvuRight, mDescriptors and mGrid
+ * (/root/reference/src/Frame.cc:709-722, AssignFeaturesToGrid :1636-1656, PosInGrid :2027-2037).  The tracking thread searches
+ * into the same frame two or three times (src/Tracking.cc:3047, :3305-3355, :2571); with a handle the train side of those calls -
+ * x / y / octave / angle / u_right, the descriptors and the 64 x 48 grid as CSR, laid out exactly as ps_proj_train documents
+ * them - is published once and neither rebuilt nor uploaded per call.
+ *
+ * Lifetimes and ordering.  The caller owns a handle from ps_frame_create to ps_frame_destroy; nothing is allocated in between.
+ * A publish replaces the content and records a "ready" event; a search that reads the handle makes its stream wait for that
+ * event and records a "last use" event behind its kernels; the next publish into the handle, and ps_frame_destroy, wait for the
+ * last uses.  Any number of matcher handles on any number of threads may read one frame handle at the same time.  Publishing
+ * is exclusive: do not publish into a handle while another thread starts a search on it, and expect every search queued after
+ * a publish to see the new frame.  A tracker keeps two handles - current frame and last frame - and alternates between them.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct ps_frame ps_frame;
+/* capacity: the most keypoints a publish may carry, 1..32767.  One device slab, one pinned staging block, a stream and events. */
+int ps_frame_create(int device, int capacity, ps_frame** out);
+void ps_frame_destroy(ps_frame* f);
+/* From host arrays: kps = mvKeysUn (cv::KeyPoint layout), u_right = mvuRight (NULL: monocular, all -1), desc = mDescriptors rows,
+ * min_x .. grid_h_inv = mnMinX, mnMinY, mfGridElementWidthInv, mfGridElementHeightInv.  One staged asynchronous upload and one
+ * kernel; returns as soon as both are queued.  n > capacity: PS_ERR_CAPACITY. */
+int ps_frame_publish_host(ps_frame* f, const ps_keypoint* kps, const float* u_right, const uint8_t* desc, int n,
+                          float min_x, float min_y, float grid_w_inv, float grid_h_inv);
+/* From an extractor handle's last results, which are still in HBM (ps_orb_batch_device_outputs / ps_orb_stereo_device_outputs):
+ * no host round trip, one launch for all frames (per 16).  image[k] = the left image's index in the batch, pair[k] = its index
+ * in the stereo outputs or -1 for none (all u_right -1), n[k] = the keypoint count the caller has already fetched.  The batched
+ * handle has image 2k / pair k; the reference's two-extractor layout has image 0 / pair 0 on the LEFT handle after
+ * ps_orb_stereo_match_pair.  The work is ordered behind everything queued on the extractor's own stream, and what is queued on
+ * that stream afterwards (the next batch) behind it; a batch run on a caller's stream is the caller's to order.  The kernel clamps
+ * n[k] to the device-side count; if the two differ the frame is marked, and the next call that consumes it fails with
+ * PS_ERR_INVALID.  The keypoints are the extractor's (mvKeys): they equal mvKeysUn only for rectified input (DistCoef == 0,
+ * Frame::UndistortKeyPoints src/Frame.cc:2039-2044 - every configuration of BASELINE.md). */
+int ps_frame_publish_orb(ps_frame* const* frames, int nframes, ps_orb* h, const int32_t* image, const int32_t* pair, const int32_t* n,
+                         float min_x, float min_y, float grid_w_inv, float grid_h_inv);
+/* Keypoints of the last publish (as the publisher stated them). */
+int ps_frame_count(ps_frame* f, int* n);
+/* GPU time of the last publish into the handle, upload included (HIP events on the publishing stream; blocks until it is done). */
+int ps_frame_last_publish_ms(ps_frame* f, float* ms);
+/* Test access (blocking).  what: 0 x, 1 y, 2 octave, 3 angle, 4 u_right (n x 4 bytes each), 5 descriptors (n x 32),
+ * 6 cell_off (64 * 48 + 1 int32), 7 cell_idx (n int32: the lists, then zeros for keypoints outside the grid).  *n = keypoints. */
+int ps_frame_debug_read(ps_frame* f, int what, void* out, size_t out_bytes, int* n);
+/* ps_search_by_projection / ps_fuse_search with the train side of problem p taken from frames[p] where that is non-null:
+ * x, y, octave, angle, u_right, desc, cell_off, cell_idx and the four grid parameters of probs[p].train are then ignored (they
+ * may be NULL) and train.n must equal the handle's count (else PS_ERR_INVALID).  occupied, in_bbox and match_of_train stay host
+ * arrays: they change from call to call.  frames[p] == NULL: the problem is served from its host arrays as in the plain call;
+ * a batch may mix both kinds, and one handle may back several problems.  Everything else - the wide re-run, the per-problem
+ * capacity failure, ps_matcher_last_kernel_ms - is that of the plain calls. */
+int ps_search_by_projection_frames(ps_matcher* m, ps_proj_problem* probs, ps_frame* const* frames, int nprob);
+int ps_fuse_search_frames(ps_matcher* m, ps_fuse_problem* problems, ps_frame* const* frames, int nproblems);
+
 
 /* ------------------------------------------------------------------------------------------------
  * Optimiser — replaces the hot static members of ORB_SLAM2::Optimizer

@@ -8,6 +8,7 @@
 #include <mutex>
 #include <string.h>
 #include <vector>
+#include "frame_host.h"
 #include "match_plan.h"
 #include "ps_common.h"
 
@@ -18,6 +19,7 @@ void psk_hamming_matrix_launch(const uint8_t*, int, const uint8_t*, int, uint16_
 void psk_pj_launch(const PjArrays*, int, int, int, int, int, hipStream_t);
 void psk_fuse_launch(const FuArrays*, int, int, hipStream_t);
 void psk_distinctive_launch(const uint8_t*, const int32_t*, int32_t*, int, hipStream_t);
+void psk_frame_stage_launch(const FrameStageJob*, int, const FrameStageDst*, hipStream_t);
 }
 
 struct ps_matcher {
@@ -57,6 +59,57 @@ int ensure(ps_matcher* m, size_t need) {
     m->h_bytes = bytes;
   }
   return PS_OK;
+}
+
+// The frame-backed problems of one search call (ps_search_by_projection_frames / ps_fuse_search_frames): which problems take their train
+// side from a frame handle, the handles each once in locking order, and a copy of what the handles said when the call looked.
+struct FrameUse {
+  std::vector<ps_frame*> of;        // per problem, nullptr = host arrays
+  std::vector<ps_frame*> uniq;
+  std::vector<FrameStageJob> jobs;  // problems with n > 0
+  std::vector<float> grid;          // [nprob][4]
+  bool all_staged = false;          // no problem needs its train arrays (or an empty grid) from the host: those bytes are not uploaded
+  bool any() const { return !uniq.empty(); }
+};
+
+int frame_use_init(FrameUse& U, ps_matcher* m, ps_frame* const* frames, int nprob, const char* what) {
+  U.of.assign(nprob, nullptr);
+  U.grid.assign((size_t)nprob * 4, 0.f);
+  if (!frames) return PS_OK;
+  for (int p = 0; p < nprob; p++) {
+    ps_frame* f = frames[p];
+    if (!f) continue;
+    if (f->device != m->device) return ps_set_error(PS_ERR_INVALID, "%s problem %d: the frame handle lives on another device", what, p);
+    U.of[p] = f;
+    U.uniq.push_back(f);
+  }
+  std::sort(U.uniq.begin(), U.uniq.end());
+  U.uniq.erase(std::unique(U.uniq.begin(), U.uniq.end()), U.uniq.end());
+  return PS_OK;
+}
+
+// train.n against the handle, and the handle's grid parameters
+int frame_use_check(FrameUse& U, int p, int train_n, const char* what) {
+  ps_frame* f = U.of[p];
+  std::lock_guard<std::mutex> lock(f->mu);
+  if (!f->published) return ps_set_error(PS_ERR_INVALID, "%s problem %d: the frame handle has never been published", what, p);
+  if (train_n != f->n) return ps_set_error(PS_ERR_INVALID, "%s problem %d: train.n = %d, the frame handle holds %d keypoints", what, p, train_n, f->n);
+  memcpy(&U.grid[(size_t)p * 4], f->grid, 16);
+  return PS_OK;
+}
+
+// queues frame_stage behind the call's upload: the slabs' train sides land where the host arrays would have been uploaded
+int frame_use_stage(FrameUse& U, ps_matcher* m, const FrameStageJob* d_jobs, const FrameStageDst& dst) {
+  int rc = psf_consume_begin(U.uniq.data(), (int)U.uniq.size(), m->stream);
+  if (rc != PS_OK) return rc;
+  hipError_t e = hipSuccess;
+  if (!U.jobs.empty()) {
+    psk_frame_stage_launch(d_jobs, (int)U.jobs.size(), &dst, m->stream);
+    e = hipGetLastError();
+  }
+  rc = psf_consume_end(U.uniq.data(), (int)U.uniq.size(), m, m->stream, !U.jobs.empty() && e == hipSuccess);
+  if (e != hipSuccess) return ps_set_error(PS_ERR_HIP, "frame_stage: %s", hipGetErrorString(e));
+  return rc;
 }
 }  // namespace
 
@@ -183,18 +236,26 @@ int ps_match_bruteforce(ps_matcher* m, ps_bf_problem* probs, int nprob, float nn
 }
 
 
-// The three ORBmatcher::SearchByProjection overloads (see include/pointslot_hip.h for the field mapping).
-int ps_search_by_projection(ps_matcher* m, ps_proj_problem* probs, int nprob) {
+// The three ORBmatcher::SearchByProjection overloads (see include/pointslot_hip.h for the field mapping).  frames: nullptr, or per
+// problem the frame handle its train side comes from (ps_search_by_projection_frames).
+static int search_by_projection(ps_matcher* m, ps_proj_problem* probs, ps_frame* const* frames, int nprob) {
   if (!m || !probs || nprob < 1) return ps_set_error(PS_ERR_INVALID, "ps_search_by_projection: bad argument");
   std::lock_guard<std::mutex> lock(m->mu);
   PS_HIP(hipSetDevice(m->device));
+  FrameUse U;
+  int frc = frame_use_init(U, m, frames, nprob, "projection");
+  if (frc != PS_OK) return frc;
   size_t NT = 0, NQ = 0;
   int max_nq = 0, max_nt = 0, any_frame = 0;
   const int NCELL = PS_GRID_COLS * PS_GRID_ROWS;
   for (int p = 0; p < nprob; p++) {
     const ps_proj_problem& P = probs[p];
     const ps_proj_train& T = P.train;
-    if (T.n < 0 || T.n > 32767 || P.nq < 0 || (T.n > 0 && (!T.x || !T.y || !T.octave || !T.angle || !T.u_right || !T.desc ||
+    if (U.of[p]) {
+      if (T.n < 0 || P.nq < 0 || (T.n > 0 && (!T.occupied || !P.match_of_train)))
+        return ps_set_error(PS_ERR_INVALID, "projection problem %d: bad train side (occupied and match_of_train stay host arrays)", p);
+      if ((frc = frame_use_check(U, p, T.n, "projection")) != PS_OK) return frc;
+    } else if (T.n < 0 || T.n > 32767 || P.nq < 0 || (T.n > 0 && (!T.x || !T.y || !T.octave || !T.angle || !T.u_right || !T.desc ||
         !T.occupied || !T.cell_off || !T.cell_idx || !P.match_of_train)))
       return ps_set_error(PS_ERR_INVALID, "projection problem %d: bad train side (n <= 32767)", p);
     if (P.nq > 0 && (!P.q_valid || !P.q_desc || !P.q_observed)) return ps_set_error(PS_ERR_INVALID, "projection problem %d: null query arrays", p);
@@ -216,8 +277,11 @@ int ps_search_by_projection(ps_matcher* m, ps_proj_problem* probs, int nprob) {
   const size_t o_qvalid = take(NQ), o_qu = take(NQ * 4), o_qv = take(NQ * 4), o_qur = take(NQ * 4), o_qrad = take(NQ * 4), o_qrer = take(NQ * 4);
   const size_t o_qminl = take(NQ * 4), o_qmaxl = take(NQ * 4), o_qdesc = take(NQ * 32), o_qobs = take(NQ), o_qang = take(NQ * 4);
   const size_t o_qxw = take(NQ * 12), o_qoct = take(NQ * 4);
+  // (the two frame-handle slots exist only in a call that uses one: the layout of every other call is what it was)
+  const size_t o_jobs = U.any() ? take(sizeof(FrameStageJob) * nprob) : 0;
   const size_t in_bytes = off;
   const size_t o_match = take(NT * 4), o_nm = take((size_t)nprob * 4), o_ovf = take((size_t)nprob * 4);
+  const size_t o_fst = U.any() ? take((size_t)nprob * 4) : 0;
   const size_t out_end = off;
   const size_t o_cand = take(NQ * PS_PJ_CAP * 4), o_ncand = take(NQ * 4), o_qbest = take(NQ * 4), o_qbin = take(NQ), o_tt = take(NQ * 16);
   int rc = ensure(m, off);
@@ -231,6 +295,17 @@ int ps_search_by_projection(ps_matcher* m, ps_proj_problem* probs, int nprob) {
     size_t t0 = 0, q0 = 0;
     for (int p = 0; p < nprob; p++) { toff[p] = t0; qoff[p] = q0; t0 += probs[p].train.n; q0 += probs[p].nq; }
   }
+  if (U.any()) {
+    U.all_staged = true;
+    for (int p = 0; p < nprob; p++) {
+      if (U.of[p] && probs[p].train.n > 0)
+        U.jobs.push_back(FrameStageJob{U.of[p]->slab, probs[p].train.n, (int32_t)toff[p], p * (NCELL + 1), p});
+      else
+        U.all_staged = false;
+    }
+    memset(H + o_jobs, 0, sizeof(FrameStageJob) * nprob);
+    if (!U.jobs.empty()) memcpy(H + o_jobs, U.jobs.data(), sizeof(FrameStageJob) * U.jobs.size());
+  }
   // every problem fills (or zeroes) exactly its own slices of the staging buffer: independent, memcpy-bound
   ps_parallel_for(nprob, in_bytes, [&](int p) {
     const ps_proj_problem& P = probs[p];
@@ -240,13 +315,18 @@ int ps_search_by_projection(ps_matcher* m, ps_proj_problem* probs, int nprob) {
     memset(&d, 0, sizeof(d));
     d.t_off = (int32_t)t0; d.nt = T.n; d.q_off = (int32_t)q0; d.c_off = (int32_t)q0; d.nq = P.nq; d.grid_off = p * (NCELL + 1);
     d.min_x = T.min_x; d.min_y = T.min_y; d.gw_inv = T.grid_w_inv; d.gh_inv = T.grid_h_inv;
+    if (U.of[p]) { const float* g = &U.grid[(size_t)p * 4]; d.min_x = g[0]; d.min_y = g[1]; d.gw_inv = g[2]; d.gh_inv = g[3]; }
     d.th_dist = P.th_dist; d.ratio_test = P.ratio_test; d.nn_ratio = P.nn_ratio; d.check_ori = P.check_orientation;
     d.use_bbox = P.use_bbox; d.frame_mode = P.frame_mode;
     memcpy(d.tcw, P.tcw, 64); memcpy(d.tlw, P.tlw, 64);
     d.fx = P.fx; d.fy = P.fy; d.cx = P.cx; d.cy = P.cy; d.mbf = P.mbf; d.mb = P.mb;
     memcpy(d.bounds, P.bounds, 16); memcpy(d.scale, P.scale_factors, 32);
     d.th = P.th; d.mono = P.mono;
-    if (T.n > 0) {
+    if (T.n > 0 && U.of[p]) {   // x .. desc and the grid are staged on the device (frame_stage)
+      const size_t n = (size_t)T.n;
+      memcpy(H + o_tocc + t0, T.occupied, n);
+      if (T.in_bbox) memcpy(H + o_tbb + t0, T.in_bbox, n); else memset(H + o_tbb + t0, 0, n);
+    } else if (T.n > 0) {
       const size_t n = (size_t)T.n, filled = (size_t)T.cell_off[NCELL];
       memcpy(H + o_tx + t0 * 4, T.x, n * 4); memcpy(H + o_ty + t0 * 4, T.y, n * 4);
       memcpy(H + o_toct + t0 * 4, T.octave, n * 4); memcpy(H + o_tang + t0 * 4, T.angle, n * 4);
@@ -277,7 +357,19 @@ int ps_search_by_projection(ps_matcher* m, ps_proj_problem* probs, int nprob) {
   });
   uint8_t* D = m->d_buf;
   const auto tp1 = std::chrono::steady_clock::now();
-  PS_HIP(hipMemcpyAsync(D, H, in_bytes, hipMemcpyHostToDevice, m->stream));
+  if (U.all_staged) {   // everything but the train arrays and the grids
+    PS_HIP(hipMemcpyAsync(D, H, o_tx, hipMemcpyHostToDevice, m->stream));
+    PS_HIP(hipMemcpyAsync(D + o_tocc, H + o_tocc, o_coff - o_tocc, hipMemcpyHostToDevice, m->stream));
+    PS_HIP(hipMemcpyAsync(D + o_qvalid, H + o_qvalid, in_bytes - o_qvalid, hipMemcpyHostToDevice, m->stream));
+  } else {
+    PS_HIP(hipMemcpyAsync(D, H, in_bytes, hipMemcpyHostToDevice, m->stream));
+  }
+  if (U.any()) {
+    FrameStageDst dst{(float*)(D + o_tx), (float*)(D + o_ty), (int32_t*)(D + o_toct), (float*)(D + o_tang), (float*)(D + o_tur), D + o_tdesc,
+                      (int32_t*)(D + o_coff), (int32_t*)(D + o_cidx), (int32_t*)(D + o_fst)};
+    PS_HIP(hipMemsetAsync(D + o_fst, 0, (size_t)nprob * 4, m->stream));
+    if ((frc = frame_use_stage(U, m, (const FrameStageJob*)(D + o_jobs), dst)) != PS_OK) return frc;
+  }
   if (prof) PS_HIP(hipStreamSynchronize(m->stream));
   const auto tp2 = std::chrono::steady_clock::now();
   PS_HIP(hipMemsetAsync(D + o_ovf, 0, (size_t)nprob * 4, m->stream));
@@ -313,9 +405,12 @@ int ps_search_by_projection(ps_matcher* m, ps_proj_problem* probs, int nprob) {
   // the other problems of the batch keep their results.  A problem that overflows that too (or has more features) is the only one
   // that fails: nmatches = -1, its match_of_train untouched, and the call returns PS_ERR_CAPACITY after serving the rest.
   const int32_t* ovf = (const int32_t*)(H + o_ovf);
-  std::vector<int> wide, failed;
+  std::vector<int> wide, failed, stale;
+  if (U.any())
+    for (int p = 0; p < nprob; p++)
+      if (((const int32_t*)(H + o_fst))[p]) stale.push_back(p);
   for (int p = 0; p < nprob; p++)
-    if (ovf[p] > 0) (probs[p].train.n <= PS_PJ_WIDE_MAX_N ? wide : failed).push_back(p);
+    if (ovf[p] > 0 && std::find(stale.begin(), stale.end(), p) == stale.end()) (probs[p].train.n <= PS_PJ_WIDE_MAX_N ? wide : failed).push_back(p);
   std::vector<int32_t> wide_nm(wide.size(), 0);
   if (!wide.empty()) {
     size_t nq2 = 0;
@@ -355,17 +450,27 @@ int ps_search_by_projection(ps_matcher* m, ps_proj_problem* probs, int nprob) {
   }
   for (int p = 0; p < nprob; p++) {
     ps_proj_problem& P = probs[p];
-    if (std::find(failed.begin(), failed.end(), p) != failed.end()) { P.nmatches = -1; continue; }
+    if (std::find(failed.begin(), failed.end(), p) != failed.end() || std::find(stale.begin(), stale.end(), p) != stale.end()) { P.nmatches = -1; continue; }
     if (P.train.n > 0) memcpy(P.match_of_train, H + o_match + toff[p] * 4, (size_t)P.train.n * 4);
     P.nmatches = ((const int32_t*)(H + o_nm))[p];
   }
   for (size_t i = 0; i < wide.size(); i++)
     if (wide_nm[i] >= 0) probs[wide[i]].nmatches = wide_nm[i];
+  if (!stale.empty())
+    return ps_set_error(PS_ERR_INVALID, "projection problem %d (and %zu more): the frame handle does not hold the %d keypoints it was published with "
+                        "(the extractor's count differed from the n given to ps_frame_publish_orb)", stale[0], stale.size() - 1, probs[stale[0]].train.n);
   if (!failed.empty())
     return ps_set_error(PS_ERR_CAPACITY, "projection problem %d (and %zu more): a search window held more than %d candidates%s", failed[0], failed.size() - 1,
                         probs[failed[0]].train.n <= PS_PJ_WIDE_MAX_N ? PS_PJ_CAP_WIDE : PS_PJ_CAP,
                         probs[failed[0]].train.n <= PS_PJ_WIDE_MAX_N ? "" : " and the frame has more features than the wide candidate store indexes (8191)");
   return PS_OK;
+}
+
+
+int ps_search_by_projection(ps_matcher* m, ps_proj_problem* probs, int nprob) { return search_by_projection(m, probs, nullptr, nprob); }
+
+int ps_search_by_projection_frames(ps_matcher* m, ps_proj_problem* probs, ps_frame* const* frames, int nprob) {
+  return search_by_projection(m, probs, frames, nprob);
 }
 
 
@@ -392,17 +497,23 @@ int ps_distinctive_descriptors(ps_matcher* m, const uint8_t* desc, const int32_t
 }
 
 
-int ps_fuse_search(ps_matcher* m, ps_fuse_problem* probs, int nprob) {
+static int fuse_search(ps_matcher* m, ps_fuse_problem* probs, ps_frame* const* frames, int nprob) {
   if (!m || !probs || nprob < 1) return ps_set_error(PS_ERR_INVALID, "ps_fuse_search: bad argument");
   std::lock_guard<std::mutex> lock(m->mu);
   PS_HIP(hipSetDevice(m->device));
+  FrameUse U;
+  int frc = frame_use_init(U, m, frames, nprob, "fuse");
+  if (frc != PS_OK) return frc;
   size_t NT = 0, NQ = 0;
   int max_nq = 0;
   const int NCELL = PS_GRID_COLS * PS_GRID_ROWS;
   for (int p = 0; p < nprob; p++) {
     const ps_fuse_problem& P = probs[p];
     const ps_proj_train& T = P.train;
-    if (T.n < 0 || P.nq < 0 || (T.n > 0 && (!T.x || !T.y || !T.octave || !T.u_right || !T.desc || !T.cell_off || !T.cell_idx)))
+    if (U.of[p]) {
+      if (T.n < 0 || P.nq < 0) return ps_set_error(PS_ERR_INVALID, "fuse problem %d: bad keyframe side", p);
+      if ((frc = frame_use_check(U, p, T.n, "fuse")) != PS_OK) return frc;
+    } else if (T.n < 0 || P.nq < 0 || (T.n > 0 && (!T.x || !T.y || !T.octave || !T.u_right || !T.desc || !T.cell_off || !T.cell_idx)))
       return ps_set_error(PS_ERR_INVALID, "fuse problem %d: bad keyframe side", p);
     if (P.nq > 0 && (!P.q_valid || !P.q_pos || !P.q_normal || !P.q_min_dist || !P.q_max_dist || !P.q_desc || !P.best_idx || !P.best_dist))
       return ps_set_error(PS_ERR_INVALID, "fuse problem %d: null query arrays", p);
@@ -417,12 +528,15 @@ int ps_fuse_search(ps_matcher* m, ps_fuse_problem* probs, int nprob) {
   const size_t o_tx = take(NT * 4), o_ty = take(NT * 4), o_toct = take(NT * 4), o_tur = take(NT * 4), o_tdesc = take(NT * 32);
   const size_t o_coff = take((size_t)nprob * (NCELL + 1) * 4), o_cidx = take(NT * 4);
   const size_t o_qvalid = take(NQ), o_qpos = take(NQ * 12), o_qnor = take(NQ * 12), o_qmin = take(NQ * 4), o_qmax = take(NQ * 4), o_qdesc = take(NQ * 32);
+  const size_t o_jobs = U.any() ? take(sizeof(FrameStageJob) * nprob) : 0;
   const size_t in_bytes = off;
   const size_t o_bi = take(NQ * 4), o_bd = take(NQ * 4);
+  const size_t o_fst = U.any() ? take((size_t)nprob * 4) : 0;
   int rc = ensure(m, off);
   if (rc != PS_OK) return rc;
   uint8_t* H = m->h_buf;
   memset(H, 0, in_bytes);
+  U.all_staged = U.any();
   FuProb* hp = (FuProb*)(H + o_prob);
   size_t t0 = 0, q0 = 0;
   for (int p = 0; p < nprob; p++) {
@@ -431,17 +545,23 @@ int ps_fuse_search(ps_matcher* m, ps_fuse_problem* probs, int nprob) {
     FuProb& d = hp[p];
     d.t_off = (int32_t)t0; d.nt = T.n; d.q_off = (int32_t)q0; d.nq = P.nq; d.grid_off = p * (NCELL + 1);
     d.min_x = T.min_x; d.min_y = T.min_y; d.gw_inv = T.grid_w_inv; d.gh_inv = T.grid_h_inv;
+    if (U.of[p]) { const float* g = &U.grid[(size_t)p * 4]; d.min_x = g[0]; d.min_y = g[1]; d.gw_inv = g[2]; d.gh_inv = g[3]; }
     memcpy(d.R, P.rcw, 36); memcpy(d.t, P.tcw, 12); memcpy(d.ow, P.ow, 12);
     d.fx = P.fx; d.fy = P.fy; d.cx = P.cx; d.cy = P.cy; d.bf = P.bf;
     memcpy(d.bounds, P.bounds, 32); memcpy(d.scale, P.scale_factors, 32); memcpy(d.inv_sigma2, P.inv_level_sigma2, 32);
     d.log_scale = P.log_scale_factor; d.n_levels = P.n_levels; d.th = P.th;
-    if (T.n > 0) {
+    if (U.of[p] && T.n > 0) {   // staged on the device (frame_stage)
+      U.jobs.push_back(FrameStageJob{U.of[p]->slab, T.n, (int32_t)t0, p * (NCELL + 1), p});
+    } else if (U.any()) {
+      U.all_staged = false;
+    }
+    if (T.n > 0 && !U.of[p]) {
       memcpy(H + o_tx + t0 * 4, T.x, (size_t)T.n * 4); memcpy(H + o_ty + t0 * 4, T.y, (size_t)T.n * 4);
       memcpy(H + o_toct + t0 * 4, T.octave, (size_t)T.n * 4); memcpy(H + o_tur + t0 * 4, T.u_right, (size_t)T.n * 4);
       memcpy(H + o_tdesc + t0 * 32, T.desc, (size_t)T.n * 32);
       memcpy(H + o_cidx + t0 * 4, T.cell_idx, (size_t)T.cell_off[NCELL] * 4);
     }
-    if (T.cell_off) memcpy(H + o_coff + (size_t)d.grid_off * 4, T.cell_off, (size_t)(NCELL + 1) * 4);
+    if (T.cell_off && !U.of[p]) memcpy(H + o_coff + (size_t)d.grid_off * 4, T.cell_off, (size_t)(NCELL + 1) * 4);
     if (P.nq > 0) {
       memcpy(H + o_qvalid + q0, P.q_valid, P.nq); memcpy(H + o_qpos + q0 * 12, P.q_pos, (size_t)P.nq * 12);
       memcpy(H + o_qnor + q0 * 12, P.q_normal, (size_t)P.nq * 12); memcpy(H + o_qmin + q0 * 4, P.q_min_dist, (size_t)P.nq * 4);
@@ -450,7 +570,19 @@ int ps_fuse_search(ps_matcher* m, ps_fuse_problem* probs, int nprob) {
     t0 += T.n; q0 += P.nq;
   }
   uint8_t* D = m->d_buf;
-  PS_HIP(hipMemcpyAsync(D, H, in_bytes, hipMemcpyHostToDevice, m->stream));
+  if (U.any() && !U.jobs.empty()) memcpy(H + o_jobs, U.jobs.data(), sizeof(FrameStageJob) * U.jobs.size());
+  if (U.all_staged) {   // everything but the keyframe arrays and the grids
+    PS_HIP(hipMemcpyAsync(D, H, o_tx, hipMemcpyHostToDevice, m->stream));
+    PS_HIP(hipMemcpyAsync(D + o_qvalid, H + o_qvalid, in_bytes - o_qvalid, hipMemcpyHostToDevice, m->stream));
+  } else {
+    PS_HIP(hipMemcpyAsync(D, H, in_bytes, hipMemcpyHostToDevice, m->stream));
+  }
+  if (U.any()) {
+    FrameStageDst dst{(float*)(D + o_tx), (float*)(D + o_ty), (int32_t*)(D + o_toct), nullptr, (float*)(D + o_tur), D + o_tdesc,
+                      (int32_t*)(D + o_coff), (int32_t*)(D + o_cidx), (int32_t*)(D + o_fst)};
+    PS_HIP(hipMemsetAsync(D + o_fst, 0, (size_t)nprob * 4, m->stream));
+    if ((frc = frame_use_stage(U, m, (const FrameStageJob*)(D + o_jobs), dst)) != PS_OK) return frc;
+  }
   FuArrays A;
   A.prob = (const FuProb*)(D + o_prob);
   A.tx = (const float*)(D + o_tx); A.ty = (const float*)(D + o_ty); A.toct = (const int32_t*)(D + o_toct); A.tur = (const float*)(D + o_tur);
@@ -462,15 +594,27 @@ int ps_fuse_search(ps_matcher* m, ps_fuse_problem* probs, int nprob) {
   PS_HIP(hipMemcpyAsync(H + o_bi, D + o_bi, off - o_bi, hipMemcpyDeviceToHost, m->stream));
   PS_HIP(hipStreamSynchronize(m->stream));
   q0 = 0;
+  int stale = -1;
   for (int p = 0; p < nprob; p++) {
     ps_fuse_problem& P = probs[p];
-    if (P.nq > 0) {
+    if (U.any() && ((const int32_t*)(H + o_fst))[p]) {   // its outputs stay as the caller left them
+      stale = stale < 0 ? p : stale;
+    } else if (P.nq > 0) {
       memcpy(P.best_idx, H + o_bi + q0 * 4, (size_t)P.nq * 4);
       memcpy(P.best_dist, H + o_bd + q0 * 4, (size_t)P.nq * 4);
     }
     q0 += P.nq;
   }
+  if (stale >= 0)
+    return ps_set_error(PS_ERR_INVALID, "fuse problem %d: the frame handle does not hold the %d keypoints it was published with "
+                        "(the extractor's count differed from the n given to ps_frame_publish_orb)", stale, probs[stale].train.n);
   return PS_OK;
+}
+
+int ps_fuse_search(ps_matcher* m, ps_fuse_problem* probs, int nprob) { return fuse_search(m, probs, nullptr, nprob); }
+
+int ps_fuse_search_frames(ps_matcher* m, ps_fuse_problem* probs, ps_frame* const* frames, int nprob) {
+  return fuse_search(m, probs, frames, nprob);
 }
 
 }  // extern "C"

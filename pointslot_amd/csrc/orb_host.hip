@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 #include "../../include/pointslot_hip.h"
+#include "frame_host.h"
 #include "orb_plan.h"
 #include "ps_common.h"
 
@@ -810,6 +811,15 @@ int ps_orb_stereo_device_outputs(const ps_orb* h, const float** d_uright, const 
   if (d_uright) *d_uright = h->d_uright;
   if (d_depth) *d_depth = h->d_depth;
   if (d_kept) *d_kept = h->d_kept;
+  return PS_OK;
+}
+
+// Internal (frame_host.hip): the device-resident results and the stream their producers were queued on.
+int psk_orb_view(ps_orb* h, PsOrbView* v) {
+  if (!h || !v) return ps_set_error(PS_ERR_INVALID, "null argument");
+  v->d_kps = h->d_kps; v->d_desc = h->d_desc; v->d_counts = h->d_counts; v->d_uright = h->d_uright;
+  v->kp_cap = h->plan.kp_cap; v->max_batch = h->cfg.max_batch; v->device = h->cfg.device; v->planned = h->planned ? 1 : 0;
+  v->stream = h->stream;
   return PS_OK;
 }
 

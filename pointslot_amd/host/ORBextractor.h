@@ -67,6 +67,16 @@ class ORBextractor {
   bool mbDownloadPyramid = true;           // not in the reference: see operator()
   ps_orb* handle() { return h_; }          // for the device-resident stereo matcher
 
+  // Not in the reference: publishes the frame this (LEFT) extractor has just extracted - and, with stereo, matched against the
+  // right one by ps_orb_stereo_match_pair - into a caller-owned frame handle without leaving the device: keypoints, descriptors
+  // and mvuRight are still in HBM.  n = keypoints.size() of operator(); the grid parameters are the Frame's mnMinX, mnMinY,
+  // mfGridElementWidthInv, mfGridElementHeightInv.  The keypoints are mvKeys: equal to mvKeysUn for rectified input only.
+  void PublishFrame(ps_frame* frame, int n, float minX, float minY, float gridElementWidthInv, float gridElementHeightInv, bool stereo = true) {
+    const int32_t image = 0, pair = stereo ? 0 : -1, count = n;
+    if (ps_frame_publish_orb(&frame, 1, h_, &image, &pair, &count, minX, minY, gridElementWidthInv, gridElementHeightInv) != PS_OK)
+      throw std::runtime_error(std::string("ps_frame_publish_orb: ") + ps_last_error());
+  }
+
  protected:
   ps_orb* h_ = nullptr;
   int nfeatures_, nlevels_;

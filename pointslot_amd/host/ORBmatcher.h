@@ -8,6 +8,8 @@
 #include <cstring>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 #include "../../include/pointslot_hip.h"
 #include "slotcv.h"
@@ -65,8 +67,9 @@ class ORBmatcher {
   static void ConfigureProjectionObject(ps_proj_problem& p, float nnratio) {                 // (Frame& F, nOrder, const vector<MapObjectPoint*>&, th)
     p.frame_mode = 0; p.th_dist = TH_HIGH_FORDYNAMIC; p.ratio_test = 1; p.nn_ratio = nnratio; p.check_orientation = 0; p.use_bbox = 1;
   }
-  int SearchByProjectionFrame(ps_proj_problem& p) { ConfigureProjectionFrame(p, mfNNratio, mbCheckOrientation); return run(p); }
-  int SearchByProjectionPoints(ps_proj_problem& p) { ConfigureProjectionPoints(p, mfNNratio); return run(p); }
+  // frame: nullptr, or the frame handle the train side of p comes from (ps_search_by_projection_frames)
+  int SearchByProjectionFrame(ps_proj_problem& p, ps_frame* frame = nullptr) { ConfigureProjectionFrame(p, mfNNratio, mbCheckOrientation); return run(p, frame); }
+  int SearchByProjectionPoints(ps_proj_problem& p, ps_frame* frame = nullptr) { ConfigureProjectionPoints(p, mfNNratio); return run(p, frame); }
   int SearchByProjectionObject(ps_proj_problem& p) { ConfigureProjectionObject(p, mfNNratio); return run(p); }
   // already-configured problems (possibly of different overloads / matcher settings) in one call; returns the summed match count
   int SearchByProjectionBatch(ps_proj_problem* p, int n) {
@@ -75,6 +78,19 @@ class ORBmatcher {
     int total = 0;
     for (int i = 0; i < n; i++) total += p[i].nmatches;
     return total;
+  }
+  // ... with the train side of problem i taken from frames[i] where that is non-null
+  int SearchByProjectionBatch(ps_proj_problem* p, ps_frame* const* frames, int n) {
+    if (n <= 0) return 0;
+    if (ps_search_by_projection_frames(h_, p, frames, n) != PS_OK) throw std::runtime_error(ps_last_error());
+    int total = 0;
+    for (int i = 0; i < n; i++) total += p[i].nmatches;
+    return total;
+  }
+  // the search half of Fuse on caller-filled problems (include/pointslot_hip.h: ps_fuse_problem); frames as above, or nullptr
+  void FuseSearch(ps_fuse_problem* p, ps_frame* const* frames, int n) {
+    if (n <= 0) return;
+    if ((frames ? ps_fuse_search_frames(h_, p, frames, n) : ps_fuse_search(h_, p, n)) != PS_OK) throw std::runtime_error(ps_last_error());
   }
   ps_matcher* handle() { return h_; }   // (kernel time of the last call: ps_matcher_last_kernel_ms)
   static float RadiusByViewingCos(const float& viewCos) { return viewCos > 0.998 ? 2.5f : 4.0f; }   // ORBmatcher.cc:252-258
@@ -86,13 +102,18 @@ class ORBmatcher {
   // mvScaleFactors, and the per-object mvObjKeys / mvObjKeysUn / mvuObjKeysRight / mvObjPointsDescriptors /
   // mvpMapObjectPoints / mvbObjKeysOutlier / mvObjKeysGrid / isInBBox).  Each does what INTEGRATION.md section 2 lists:
   // gather the fields the reference reads into a ps_proj_problem / ps_bf_problem, one C-ABI call, pointer write-back.
+  // A Frame type with a member `ps_frame* mpDeviceFrame` (not in the reference; detected at compile time) that is non-null
+  // has its train side on the device already: the two overloads that search into the frame's own keypoints then build no host
+  // CSR and pack no train arrays - only mvpMapPoints' occupancy travels.  (The object overload searches into one object's
+  // key set, which a frame handle does not hold.)
   // ------------------------------------------------------------------------------------------------------------------
 
   // int SearchByProjection(Frame &F, const vector<MapPoint*> &vpMapPoints, const float th)            ORBmatcher.cc:68-155
   template <class FrameT, class MapPointT>
   int SearchByProjection(FrameT& F, const std::vector<MapPointT*>& vpMapPoints, const float th) {
     TrainSide T;
-    fillTrain(T, F.mvKeysUn, F.mvuRight, F.mDescriptors, F.mGrid, F);
+    T.frame = deviceFrameOf(F);
+    if (T.frame) fillTrainOnDevice(T, (int)F.mvKeysUn.size()); else fillTrain(T, F.mvKeysUn, F.mvuRight, F.mDescriptors, F.mGrid, F);
     for (size_t j = 0; j < F.mvpMapPoints.size(); j++) T.occupied[j] = (F.mvpMapPoints[j] && F.mvpMapPoints[j]->Observations() > 0) ? 1 : 0;
     return searchPoints(T, F, vpMapPoints, th, false, [&](int j, MapPointT* p) { F.mvpMapPoints[j] = p; });
   }
@@ -115,7 +136,9 @@ class ORBmatcher {
   template <class FrameT>
   int SearchByProjection(FrameT& CurrentFrame, const FrameT& LastFrame, const float th, const bool bMono) {
     TrainSide T;
-    fillTrain(T, CurrentFrame.mvKeysUn, CurrentFrame.mvuRight, CurrentFrame.mDescriptors, CurrentFrame.mGrid, CurrentFrame);
+    T.frame = deviceFrameOf(CurrentFrame);
+    if (T.frame) fillTrainOnDevice(T, (int)CurrentFrame.mvKeysUn.size());
+    else fillTrain(T, CurrentFrame.mvKeysUn, CurrentFrame.mvuRight, CurrentFrame.mDescriptors, CurrentFrame.mGrid, CurrentFrame);
     for (size_t j = 0; j < CurrentFrame.mvpMapPoints.size(); j++)
       T.occupied[j] = (CurrentFrame.mvpMapPoints[j] && CurrentFrame.mvpMapPoints[j]->Observations() > 0) ? 1 : 0;
     const int nq = LastFrame.N;
@@ -143,7 +166,7 @@ class ORBmatcher {
     p.th = th;
     std::vector<int32_t> match((size_t)std::max(T.n, 1), -1);
     p.match_of_train = match.data();
-    const int n = SearchByProjectionFrame(p);
+    const int n = SearchByProjectionFrame(p, T.frame);
     for (int j = 0; j < T.n; j++) {
       if (match[j] >= 0) CurrentFrame.mvpMapPoints[j] = LastFrame.mvpMapPoints[match[j]];
       else if (match[j] == -2) CurrentFrame.mvpMapPoints[j] = NULL;   // assigned, then reset by the rotation check (:1742-1750)
@@ -187,6 +210,7 @@ class ORBmatcher {
     std::vector<int32_t> octave, cell_off, cell_idx;
     std::vector<uint8_t> desc, occupied, in_bbox;
     float min_x = 0, min_y = 0, gw = 0, gh = 0;
+    ps_frame* frame = nullptr;   // non-null: everything but occupied / in_bbox is in this handle, the vectors above stay empty
     void bind(ps_proj_train& t) const {
       t.n = n; t.x = x.data(); t.y = y.data(); t.octave = octave.data(); t.angle = angle.data(); t.u_right = ur.data(); t.desc = desc.data();
       t.occupied = occupied.data(); t.in_bbox = in_bbox.empty() ? nullptr : in_bbox.data(); t.cell_off = cell_off.data(); t.cell_idx = cell_idx.data();
@@ -202,6 +226,13 @@ class ORBmatcher {
     for (int r = 0; r < 4; r++)
       for (int c = 0; c < 4; c++) out16[4 * r + c] = Tcw.template at<float>(r, c);
   }
+  // ps_frame* mpDeviceFrame of the caller's Frame type, nullptr for a type without the member
+  template <class T, class = void> struct HasDeviceFrame : std::false_type {};
+  template <class T> struct HasDeviceFrame<T, std::void_t<decltype(std::declval<const T&>().mpDeviceFrame)>> : std::true_type {};
+  template <class FrameT> static ps_frame* deviceFrameOf(const FrameT& F) {
+    if constexpr (HasDeviceFrame<FrameT>::value) return F.mpDeviceFrame; else return nullptr;
+  }
+  static void fillTrainOnDevice(TrainSide& T, int n) { T.n = n; T.occupied.assign(std::max(n, 1), 0); }
   template <class KeysT, class GridT, class FrameT>
   static void fillTrain(TrainSide& T, const KeysT& keysUn, const std::vector<float>& uRight, const pscv::Mat& descriptors, const GridT& grid, const FrameT& F) {
     const int n = (int)keysUn.size();
@@ -257,14 +288,14 @@ class ORBmatcher {
     std::vector<int32_t> match((size_t)std::max(T.n, 1), -1);
     p.match_of_train = match.data();
     if (nq == 0) return 0;
-    const int n = object ? SearchByProjectionObject(p) : SearchByProjectionPoints(p);
+    const int n = object ? SearchByProjectionObject(p) : SearchByProjectionPoints(p, T.frame);
     for (int j = 0; j < T.n; j++)
       if (match[j] >= 0) assign(j, pts[match[j]]);
     return n;
   }
 
-  int run(ps_proj_problem& p) {
-    if (ps_search_by_projection(h_, &p, 1) != PS_OK) throw std::runtime_error(ps_last_error());
+  int run(ps_proj_problem& p, ps_frame* frame = nullptr) {
+    if ((frame ? ps_search_by_projection_frames(h_, &p, &frame, 1) : ps_search_by_projection(h_, &p, 1)) != PS_OK) throw std::runtime_error(ps_last_error());
     return p.nmatches;
   }
   ps_matcher* h_ = nullptr;

@@ -18,6 +18,7 @@
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
+#include <cstdlib>
 #include <cstring>
 #include <functional>
 #include <memory>
@@ -72,6 +73,7 @@ class OdoSequence {
   bool lastFrameTracked = false;
 
   ps_proj_problem proj;     // the pending SearchByProjection problem (Request SEARCH)
+  ps_frame* deviceFrame = nullptr;   // set before begin(): the current frame is published in this handle; the driver serves proj through it
   ps_pose_problem posep;    // the pending PoseOptimization problem (Request POSE)
 
   // Tracking::Track up to the first device request.  F holds the extraction results (mvKeys, mDescriptors, mvuRight, mvDepth).
@@ -222,7 +224,7 @@ class OdoSequence {
     const int GC = OdoCamera::GRID_COLS, GR = OdoCamera::GRID_ROWS;
     std::vector<int> cell(Fr.N, -1);
     Fr.cell_off.assign(GC * GR + 1, 0);
-    for (int i = 0; i < Fr.N; i++) {
+    for (int i = 0; i < Fr.N && !deviceFrame; i++) {   // (with a frame handle the grid is built on the device)
       const int px = (int)std::round((Fr.x[i] - 0.f) * cam->gwInv), py = (int)std::round((Fr.y[i] - 0.f) * cam->ghInv);
       if (px < 0 || px >= GC || py < 0 || py >= GR) continue;
       cell[i] = px * GR + py;
@@ -380,13 +382,23 @@ class StereoOdometry {
   static const State NOT_INITIALIZED = OdoSequence::NOT_INITIALIZED, OK = OdoSequence::OK, LOST = OdoSequence::LOST;
 
   StereoOdometry(float fx, float fy, float cx, float cy, float bf, int width, int height, float thDepth = 35.f, int nFeatures = 2000,
-                 float scale = 1.2f, int nLevels = 8, int iniTh = 20, int minTh = 5)
+                 float scale = 1.2f, int nLevels = 8, int iniTh = 20, int minTh = 5, bool deviceFrames = false)
       : left(nFeatures, scale, nLevels, iniTh, minTh), right(nFeatures, scale, nLevels, iniTh, minTh), matcher(0.9f, true),
         cam(fx, fy, cx, cy, bf, width, height, thDepth, left.GetScaleFactors(), left.GetInverseScaleSigmaSquares()), seq(&cam),
         state(seq.state), trajectory(seq.trajectory), lastMatches(seq.lastMatches), lastMapMatches(seq.lastMapMatches),
         lastLocalInliers(seq.lastLocalInliers) {
     left.mbDownloadPyramid = false; right.mbDownloadPyramid = false;
+    // opt-in (off by default): the current frame is published once into a frame handle after ComputeStereoMatches and its 2-3
+    // searches read it there; two handles, current and last, alternate.  Also switched on by PS_ODO_DEVICE_FRAMES=1.
+    const char* env = getenv("PS_ODO_DEVICE_FRAMES");
+    if (deviceFrames || (env && atoi(env) != 0)) {
+      const int cap = nFeatures + 4 * nLevels + 64;   // what ORBextractor::operator() can return
+      for (int k = 0; k < 2; k++)
+        if (ps_frame_create(0, cap, &frames[k]) != PS_OK) throw std::runtime_error(std::string("ps_frame_create: ") + ps_last_error());
+    }
   }
+  ~StereoOdometry() { for (int k = 0; k < 2; k++) ps_frame_destroy(frames[k]); }
+  bool usesDeviceFrames() const { return frames[0] != nullptr; }
 
   // Where a frame's wall time goes ("marshaling to SoA every call must be measured and reported separately from kernel
   // time"), accumulated over Track calls: wall seconds inside the C-ABI calls by kind, the kernels' own time inside the matcher / optimiser
@@ -419,6 +431,12 @@ class StereoOdometry {
     int n = 0;
     if (N > 0 && ps_orb_stereo_match_pair(left.handle(), right.handle(), cam.mb, cam.mbf, F->mvuRight.data(), F->mvDepth.data(), N, &n) != PS_OK)
       throw std::runtime_error(ps_last_error());                                         // Frame::ComputeStereoMatches
+    seq.deviceFrame = nullptr;
+    if (frames[0] && N > 0) {   // keypoints, descriptors and mvuRight are still in HBM (counted with the stereo matcher's time)
+      seq.deviceFrame = frames[flip];
+      flip ^= 1;
+      left.PublishFrame(seq.deviceFrame, N, 0.f, 0.f, cam.gwInv, cam.ghInv);
+    }
     const auto t2 = clk::now();
     split.extract += secs(t0, t1); split.stereo += secs(t1, t2);
     double inCalls = 0;
@@ -427,7 +445,8 @@ class StereoOdometry {
       const auto a = clk::now();
       float kms = 0;
       if (rq == OdoSequence::SEARCH) {
-        matcher.SearchByProjectionBatch(&seq.proj, 1);
+        if (seq.deviceFrame) matcher.SearchByProjectionBatch(&seq.proj, &seq.deviceFrame, 1);
+        else matcher.SearchByProjectionBatch(&seq.proj, 1);
         const double d = secs(a, clk::now());
         ps_matcher_last_kernel_ms(matcher.handle(), &kms);
         split.search += d; split.searchKernelMs += kms; split.searchCalls++; inCalls += d;
@@ -452,6 +471,8 @@ class StereoOdometry {
   ORBmatcher matcher;
   OdoCamera cam;
   OdoSequence seq;
+  ps_frame* frames[2] = {nullptr, nullptr};
+  int flip = 0;
 
  public:
   State& state;

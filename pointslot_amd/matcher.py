@@ -145,7 +145,30 @@ def _arr(a, dt):
     return np.ascontiguousarray(a, dt)
 
 
+def _fill_train_from_frame(p, F, keep):
+    """the train side lives in a DeviceFrame (F["frame"]): only what changes from call to call comes from the host"""
+    n = len(F["frame"])
+    a = dict(occupied=_arr(F.get("occupied", np.zeros(n, np.uint8)), np.uint8), in_bbox=_arr(F.get("in_bbox", np.ones(n, np.uint8)), np.uint8))
+    if len(a["occupied"]) != n or len(a["in_bbox"]) != n:
+        raise ValueError("occupied / in_bbox must have one entry per keypoint of the frame (%d)" % n)
+    keep.append(a)
+    p.train.n = n
+    for k, v in a.items():
+        setattr(p.train, k, v.ctypes.data)
+    return n
+
+
+def _frame_handles(problems):
+    """(ctypes array of ps_frame* or None per problem) when any problem of the batch is frame-backed, else None"""
+    fr = [pr["train"].get("frame") for pr in problems]
+    if all(f is None for f in fr):
+        return None
+    return (ctypes.c_void_p * len(fr))(*[None if f is None else f._h.value for f in fr])
+
+
 def _fill_train(p, F, keep):
+    if F.get("frame") is not None:
+        return _fill_train_from_frame(p, F, keep)
     n = len(F["x"])
     a = dict(x=_arr(F["x"], np.float32), y=_arr(F["y"], np.float32), octave=_arr(F["octave"], np.int32),
              angle=_arr(F["angle"], np.float32), u_right=_arr(F["u_right"], np.float32),
@@ -161,58 +184,76 @@ def _fill_train(p, F, keep):
     return n
 
 
-def _search_by_projection(self, problems, partial_ok=False):
-    """problems: list of dicts, see SearchByProjectionFrame / SearchByProjectionPoints for the two layouts.  partial_ok: when a
-    problem overflows even the wide candidate store the call fails with PS_ERR_CAPACITY after serving all the others; with
-    partial_ok the results come back anyway, nmatches = -1 marking the problems that failed."""
+def _prepare_projection(self, problems):
+    """the ps_proj_problem array of a batch: (array, frame handles or None, buffers to keep alive, outputs)"""
     n = len(problems)
     arr = (_ProjProblem * n)()
     keep, outs = [], []
     for i, pr in enumerate(problems):
-        p = arr[i]
-        nt = _fill_train(p, pr["train"], keep)
-        q = pr["query"]
-        nq = len(q["valid"])
-        a = dict(q_valid=_arr(q["valid"], np.uint8), q_desc=_arr(q["desc"], np.uint8).reshape(-1, 32),
-                 q_observed=_arr(q["observed"], np.uint8))
-        p.frame_mode = 1 if pr["mode"] == "frame" else 0
-        if p.frame_mode:
-            a.update(q_angle=_arr(q["angle"], np.float32), q_xw=_arr(q["xw"], np.float32), q_octave=_arr(q["octave"], np.int32))
-            p.tcw = (ctypes.c_float * 16)(*np.asarray(pr["tcw"], np.float32).reshape(16))
-            p.tlw = (ctypes.c_float * 16)(*np.asarray(pr["tlw"], np.float32).reshape(16))
-            p.fx, p.fy, p.cx, p.cy, p.mbf, p.mb = [float(v) for v in pr["K6"]]
-            p.bounds = (ctypes.c_float * 4)(*[float(v) for v in pr["bounds"]])
-            p.th = float(pr["th"]); p.mono = 1 if pr.get("mono") else 0
-            p.th_dist = ORBmatcher.TH_HIGH; p.ratio_test = 0; p.nn_ratio = self.mfNNratio
-            p.check_orientation = 1 if self.mbCheckOrientation else 0; p.use_bbox = 0
-        else:
-            obj = bool(pr.get("object"))
-            th = np.float32(pr["th"])
-            lvl = np.asarray(q["level"], np.int32)
-            sf = np.asarray(pr["scale_factors"], np.float32)
-            r = np.where(np.asarray(q["view_cos"], np.float32) > np.float32(0.998), np.float32(2.5), np.float32(4.0)).astype(np.float32)
-            if float(th) != 1.0:
-                r = (r * th).astype(np.float32)
-            rer = (r * sf[lvl]).astype(np.float32)
-            a.update(q_u=_arr(q["proj_x"], np.float32), q_v=_arr(q["proj_y"], np.float32), q_ur=_arr(q["proj_xr"], np.float32),
-                     q_radius=np.full(nq, 5.0, np.float32) if obj else rer, q_radius_er=rer,
-                     q_min_level=(lvl - 1).astype(np.int32), q_max_level=(lvl + 1 if obj else lvl).astype(np.int32))
-            p.th_dist = ORBmatcher.TH_HIGH_FORDYNAMIC if obj else ORBmatcher.TH_HIGH
-            p.ratio_test = 1; p.nn_ratio = self.mfNNratio; p.check_orientation = 0; p.use_bbox = 1 if obj else 0
-        p.scale_factors = (ctypes.c_float * 8)(*np.asarray(pr["scale_factors"], np.float32))
-        p.nq = nq
-        for k, v in a.items():
-            setattr(p, k, v.ctypes.data)
-        out = np.full(max(nt, 1), -1, np.int32)
-        p.match_of_train = out.ctypes.data
-        keep.append(a); outs.append((out, nt))
-    rc = lib.ps_search_by_projection(self._h, arr, n)
+        _fill_projection_problem(self, arr[i], pr, keep, outs)
+    return arr, _frame_handles(problems), keep, outs
+
+
+def _search_by_projection(self, problems, partial_ok=False):
+    """problems: list of dicts, see SearchByProjectionFrame / SearchByProjectionPoints for the two layouts.  A problem whose
+    train dict has "frame" = a DeviceFrame (pointslot_amd.frame) takes its train side from that handle and needs only "occupied"
+    (and "in_bbox") beside it.  partial_ok: when a
+    problem overflows even the wide candidate store the call fails with PS_ERR_CAPACITY after serving all the others; with
+    partial_ok the results come back anyway, nmatches = -1 marking the problems that failed."""
+    n = len(problems)
+    arr, frames, keep, outs = _prepare_projection(self, problems)
+    if frames is None:
+        rc = lib.ps_search_by_projection(self._h, arr, n)
+    else:
+        lib.ps_search_by_projection_frames.argtypes = [ctypes.c_void_p, ctypes.POINTER(_ProjProblem), ctypes.POINTER(ctypes.c_void_p), ctypes.c_int]
+        rc = lib.ps_search_by_projection_frames(self._h, arr, frames, n)
     if not (partial_ok and rc == -3):
         check(rc)
     return [(arr[i].nmatches, outs[i][0][:outs[i][1]].copy()) for i in range(n)]
 
 
+def _fill_projection_problem(self, p, pr, keep, outs):
+    """one ps_proj_problem from its dict (see _search_by_projection)"""
+    nt = _fill_train(p, pr["train"], keep)
+    q = pr["query"]
+    nq = len(q["valid"])
+    a = dict(q_valid=_arr(q["valid"], np.uint8), q_desc=_arr(q["desc"], np.uint8).reshape(-1, 32),
+             q_observed=_arr(q["observed"], np.uint8))
+    p.frame_mode = 1 if pr["mode"] == "frame" else 0
+    if p.frame_mode:
+        a.update(q_angle=_arr(q["angle"], np.float32), q_xw=_arr(q["xw"], np.float32), q_octave=_arr(q["octave"], np.int32))
+        p.tcw = (ctypes.c_float * 16)(*np.asarray(pr["tcw"], np.float32).reshape(16))
+        p.tlw = (ctypes.c_float * 16)(*np.asarray(pr["tlw"], np.float32).reshape(16))
+        p.fx, p.fy, p.cx, p.cy, p.mbf, p.mb = [float(v) for v in pr["K6"]]
+        p.bounds = (ctypes.c_float * 4)(*[float(v) for v in pr["bounds"]])
+        p.th = float(pr["th"]); p.mono = 1 if pr.get("mono") else 0
+        p.th_dist = ORBmatcher.TH_HIGH; p.ratio_test = 0; p.nn_ratio = self.mfNNratio
+        p.check_orientation = 1 if self.mbCheckOrientation else 0; p.use_bbox = 0
+    else:
+        obj = bool(pr.get("object"))
+        th = np.float32(pr["th"])
+        lvl = np.asarray(q["level"], np.int32)
+        sf = np.asarray(pr["scale_factors"], np.float32)
+        r = np.where(np.asarray(q["view_cos"], np.float32) > np.float32(0.998), np.float32(2.5), np.float32(4.0)).astype(np.float32)
+        if float(th) != 1.0:
+            r = (r * th).astype(np.float32)
+        rer = (r * sf[lvl]).astype(np.float32)
+        a.update(q_u=_arr(q["proj_x"], np.float32), q_v=_arr(q["proj_y"], np.float32), q_ur=_arr(q["proj_xr"], np.float32),
+                 q_radius=np.full(nq, 5.0, np.float32) if obj else rer, q_radius_er=rer,
+                 q_min_level=(lvl - 1).astype(np.int32), q_max_level=(lvl + 1 if obj else lvl).astype(np.int32))
+        p.th_dist = ORBmatcher.TH_HIGH_FORDYNAMIC if obj else ORBmatcher.TH_HIGH
+        p.ratio_test = 1; p.nn_ratio = self.mfNNratio; p.check_orientation = 0; p.use_bbox = 1 if obj else 0
+    p.scale_factors = (ctypes.c_float * 8)(*np.asarray(pr["scale_factors"], np.float32))
+    p.nq = nq
+    for k, v in a.items():
+        setattr(p, k, v.ctypes.data)
+    out = np.full(max(nt, 1), -1, np.int32)
+    p.match_of_train = out.ctypes.data
+    keep.append(a); outs.append((out, nt))
+
+
 ORBmatcher.SearchByProjection = _search_by_projection
+ORBmatcher._prepare_projection = _prepare_projection
 
 
 class _FuseProblem(ctypes.Structure):
@@ -239,8 +280,9 @@ def _fuse_search(self, problems):
     for i, pr in enumerate(problems):
         p = arr[i]
         F = dict(pr["train"])
-        nt = len(F["x"])
-        F.setdefault("angle", np.zeros(nt, np.float32)); F.setdefault("occupied", np.zeros(nt, np.uint8))
+        if F.get("frame") is None:
+            nt = len(F["x"])
+            F.setdefault("angle", np.zeros(nt, np.float32)); F.setdefault("occupied", np.zeros(nt, np.uint8))
         _fill_train(p, F, keep)
         q = pr["query"]
         m = len(q["valid"])
@@ -260,7 +302,12 @@ def _fuse_search(self, problems):
         bi = np.full(max(m, 1), -1, np.int32); bd = np.full(max(m, 1), 256, np.int32)
         p.best_idx = bi.ctypes.data; p.best_dist = bd.ctypes.data
         keep.append(a); outs.append((bi, bd, m))
-    check(lib.ps_fuse_search(self._h, arr, n))
+    frames = _frame_handles(problems)
+    if frames is None:
+        check(lib.ps_fuse_search(self._h, arr, n))
+    else:
+        lib.ps_fuse_search_frames.argtypes = [ctypes.c_void_p, ctypes.POINTER(_FuseProblem), ctypes.POINTER(ctypes.c_void_p), ctypes.c_int]
+        check(lib.ps_fuse_search_frames(self._h, arr, frames, n))
     return [(bi[:m].copy(), bd[:m].copy()) for bi, bd, m in outs]
 
 

@@ -1,0 +1,373 @@
+"""The device-resident frame handle (ps_frame / pointslot_amd.frame.DeviceFrame): what a publish leaves in HBM is bit for bit the
+SoA and the CSR grid the per-call matchers are given from the host, and a search through a handle returns what the same search
+through host arrays returns."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+gpu = pytest.mark.gpu
+SOA = ("x", "y", "octave", "angle", "u_right", "desc")
+
+
+def test_no_device_frame_without_device():
+    from pointslot_amd import _lib
+    if _lib.device_count() > 0:
+        pytest.skip("a GPU is visible")
+    from pointslot_amd.frame import DeviceFrame
+    with pytest.raises(_lib.PointslotError) as e:
+        DeviceFrame(100)
+    assert e.value.code == _lib.PS_ERR_NO_DEVICE
+
+
+# ---- helpers ------------------------------------------------------------------------------------------------------------
+def _cells_exact(x, y, grid):
+    """PosInGrid with the float32 product rounded exactly (C round, half away from zero, in float64) - what the device computes"""
+    out = []
+    for v, mn, inv in ((x, grid[0], grid[2]), (y, grid[1], grid[3])):
+        f = ((np.asarray(v, np.float32) - np.float32(mn)) * np.float32(inv)).astype(np.float64)
+        out.append(np.where(f >= 0, np.floor(f + 0.5), np.ceil(f - 0.5)).astype(np.int64))
+    return out
+
+
+def _cells_build_grid(x, y, grid):
+    """... and as pointslot_amd.matcher.build_grid evaluates it (floor(f + 0.5) in float32)"""
+    out = []
+    for v, mn, inv in ((x, grid[0], grid[2]), (y, grid[1], grid[3])):
+        f = (np.asarray(v, np.float32) - np.float32(mn)) * np.float32(inv)
+        out.append(np.where(f >= 0, np.floor(f + np.float32(0.5)), np.ceil(f - np.float32(0.5))).astype(np.int64))
+    return out
+
+
+def _assert_input_condition(x, y, grid):
+    """build_grid differs from C round for a product one ulp below a half; the cases of this file must not contain one"""
+    (ex, ey), (bx, by) = _cells_exact(x, y, grid), _cells_build_grid(x, y, grid)
+    assert np.array_equal(ex, bx) and np.array_equal(ey, by)
+
+
+def _train(x, y, grid, seed=5):
+    rng = np.random.default_rng(seed)
+    n = len(x)
+    return {"x": np.asarray(x, np.float32), "y": np.asarray(y, np.float32), "octave": rng.integers(0, 8, n).astype(np.int32),
+            "angle": rng.uniform(0, 360, n).astype(np.float32), "u_right": np.where(rng.uniform(size=n) < 0.7, rng.uniform(0, 1000, n), -1).astype(np.float32),
+            "desc": rng.integers(0, 256, (n, 32), dtype=np.uint8), "grid": tuple(np.float32(g) for g in grid)}
+
+
+def _check_published(F, tr, mono=False):
+    from pointslot_amd.matcher import build_grid
+    n = len(tr["x"])
+    _assert_input_condition(tr["x"], tr["y"], tr["grid"])
+    F.publish(tr, None if mono else tr["u_right"], tr["desc"], tr["grid"])
+    got = F.read()
+    assert got["n"] == n == len(F)
+    for k in SOA:
+        want = np.full(n, -1, np.float32) if (mono and k == "u_right") else np.asarray(tr[k])
+        assert got[k].dtype == want.dtype and np.array_equal(got[k].view(np.uint8).ravel(), np.ascontiguousarray(want).view(np.uint8).ravel()), k
+    off, idx = build_grid(tr["x"], tr["y"], *tr["grid"])
+    assert np.array_equal(got["cell_off"], off)
+    assert len(got["cell_idx"]) == n
+    assert np.array_equal(got["cell_idx"][:len(idx)], idx)
+    assert not got["cell_idx"][len(idx):].any()          # keypoints outside the grid leave a zero tail
+    return got
+
+
+_SCENE_KW = {0x51070020: {}, 0x51070021: {"n": 600, "m": 900, "th": 15.0}, 0x51070022: {"n": 50, "m": 10}}
+_cache = {}
+
+
+def _scene(seed):
+    """(frame, points, points th = 3, object) of test_match_gpu._scene_problems, computed once"""
+    if seed not in _cache:
+        from test_match_gpu import _scene_problems
+        _cache[seed] = _scene_problems(seed, **_SCENE_KW[seed])
+    return _cache[seed]
+
+
+def _expected(pr, nnratio=0.8, check_ori=True):
+    import oracle_lib
+    key = ("want", id(pr), nnratio, check_ori)
+    if key not in _cache:
+        _cache[key] = (oracle_lib.search_projection_frame(pr, check_ori) if pr["mode"] == "frame" else oracle_lib.search_projection_points(pr, nnratio), pr)
+    return _cache[key][0]
+
+
+def _through(pr, F):
+    """the same problem with its train side in the handle F: only what changes from call to call stays on the host"""
+    tr = pr["train"]
+    return dict(pr, train={"frame": F, "occupied": tr["occupied"], "in_bbox": tr["in_bbox"]})
+
+
+def _publish_scene(F, pr):
+    tr = pr["train"]
+    F.publish(tr, tr["u_right"], tr["desc"], tr["grid"])
+
+
+@pytest.fixture(scope="module")
+def matcher():
+    from pointslot_amd.matcher import ORBmatcher
+    m = ORBmatcher(0.8, True)
+    yield m
+    m.close()
+
+
+@pytest.fixture(scope="module")
+def handle():
+    from pointslot_amd.frame import DeviceFrame
+    F = DeviceFrame(4096)
+    yield F
+    F.close()
+
+
+# ---- 1. grid and SoA parity ---------------------------------------------------------------------------------------------------
+@gpu
+@pytest.mark.parametrize("n", [0, 1, 63, 64, 65, 257, 2000])
+def test_publish_host_parity(handle, n):
+    from pointslot_amd import synth
+    tr = synth.projection_scene(0x51070020 + (n % 3), n=n, m=0)["train"]
+    _check_published(handle, tr)
+
+
+@gpu
+def test_publish_host_parity_largest_frame():
+    from pointslot_amd import synth
+    from pointslot_amd.frame import DeviceFrame
+    tr = synth.projection_scene(0x51070040, n=32767, m=0)["train"]
+    F = DeviceFrame(32767)
+    _check_published(F, tr)
+    F.close()
+
+
+@gpu
+def test_publish_one_crowded_cell(handle):
+    """4000 keypoints in one cell and 96 elsewhere: a per-cell quadratic step would take the whole budget"""
+    rng = np.random.default_rng(11)
+    grid = (0.0, 0.0, 64.0 / 1241.0, 48.0 / 376.0)
+    x = np.concatenate([rng.uniform(593, 609, 4000), rng.uniform(20, 1220, 96)]).astype(np.float32)
+    y = np.concatenate([rng.uniform(177, 183, 4000), rng.uniform(20, 350, 96)]).astype(np.float32)
+    perm = rng.permutation(4096)
+    tr = _train(x[perm], y[perm], grid)
+    got = _check_published(handle, tr)
+    assert np.diff(got["cell_off"]).max() >= 4000
+
+
+@gpu
+def test_publish_half_cell_boundaries_and_outside(handle):
+    """products that are exactly k + 0.5 (round half away from zero), negative products including -0.5 (cell -1: excluded) and
+    -0.25 (rounds to -0: cell 0), keypoints beyond the last column / row; all products exactly representable"""
+    # grid_w_inv = 0.5, min_x = 0, odd integer x: the product is k + 0.5
+    xs = np.arange(1, 131, 2, dtype=np.float32); ys = np.arange(1, 99, 2, dtype=np.float32)
+    x = np.repeat(xs, len(ys)); y = np.tile(ys, len(xs))
+    tr = _train(x, y, (0.0, 0.0, 0.5, 0.5))
+    got = _check_published(handle, tr)
+    ex, ey = _cells_exact(x, y, tr["grid"])
+    assert np.array_equal(ex, (x + 1) // 2) and ex.max() == 65 and ey.max() == 49       # some land beyond the grid
+    assert got["cell_off"][-1] == int(((ex < 64) & (ey < 48)).sum()) < len(x)
+    # min_x, min_y > 0 with keypoints left of / above the origin
+    x = np.array([8.0, 7.0, 7.5, 7.75, 6.0, 9.0, 8.5, 200.0, 8.0, 7.5, 135.0, 136.0, 135.5, 10.0], np.float32)
+    y = np.array([4.0, 4.0, 4.0, 4.0, 4.0, 3.0, 3.5, 4.0, 3.0, 3.5, 99.0, 50.0, 99.5, 100.5], np.float32)
+    tr = _train(x, y, (8.0, 4.0, 0.5, 0.5))
+    got = _check_published(handle, tr)
+    ex, ey = _cells_exact(x, y, tr["grid"])
+    assert ex[1] == -1 and ex[2] == 0 and ex[3] == 0 and ex[4] == -1 and ey[5] == -1 and ey[6] == 0      # -0.5 -> -1, -0.25 -> 0
+    assert ex[10] == 64 and ex[11] == 64 and ey[13] == 48                                                # 63.5 -> 64: outside
+    inside = (ex >= 0) & (ex < 64) & (ey >= 0) & (ey < 48)
+    assert got["cell_off"][-1] == inside.sum() and 0 < inside.sum() < len(x)
+    # monocular: no u_right
+    _check_published(handle, tr, mono=True)
+
+
+# ---- 2. search parity ------------------------------------------------------------------------------------------------------------
+@gpu
+@pytest.mark.parametrize("seed", [0x51070020, 0x51070021, 0x51070022])
+def test_search_through_a_frame_equals_host_arrays(matcher, handle, seed):
+    probs = list(_scene(seed))
+    host = matcher.SearchByProjection(probs)
+    _publish_scene(handle, probs[0])
+    dev = matcher.SearchByProjection([_through(pr, handle) for pr in probs])        # one handle backs all four problems
+    for i, (pr, (nh, oh), (nd, od)) in enumerate(zip(probs, host, dev)):
+        no, oo = _expected(pr)
+        assert nh == nd == no, (i, nh, nd, no)
+        assert np.array_equal(od, oh) and np.array_equal(od, oo), i
+    assert sum(r[0] for r in dev) > (20 if seed == 0x51070022 else 500)
+
+
+@gpu
+def test_search_mixed_batch_dense_window_and_empty_frame(matcher, handle):
+    from pointslot_amd.frame import DeviceFrame
+    from test_match_gpu import _dense_window_problem
+    frame, pts, _, obj = _scene(0x51070020)
+    other = _scene(0x51070021)[1]
+    _publish_scene(handle, frame)
+    res = matcher.SearchByProjection([_through(frame, handle), other, _through(obj, handle)])
+    for pr, (n, out) in zip([frame, other, obj], res):
+        no, oo = _expected(pr)
+        assert n == no and np.array_equal(out, oo), pr["mode"]
+    # the wide re-run: 700 candidates in every window, train side from a handle, next to a host-backed problem
+    dense = _dense_window_problem(77, 700)
+    dense["train"].setdefault("in_bbox", np.ones(len(dense["train"]["x"]), np.uint8))
+    _assert_input_condition(dense["train"]["x"], dense["train"]["y"], dense["train"]["grid"])
+    D = DeviceFrame(1000)
+    _publish_scene(D, dense)
+    res = matcher.SearchByProjection([_through(dense, D), pts])
+    for pr, (n, out) in zip([dense, pts], res):
+        no, oo = _expected(pr)
+        assert n == no and np.array_equal(out, oo), pr["mode"]
+    assert res[0][0] >= 20
+    # an empty frame
+    z = np.zeros(0, np.float32)
+    D.publish({"x": z, "y": z, "octave": z, "angle": z}, z, np.zeros((0, 32), np.uint8), frame["train"]["grid"])
+    empty = dict(_scene(0x51070022)[1], train={"frame": D, "occupied": np.zeros(0, np.uint8)})      # 10 queries, nothing to match into
+    (n0, out0), (n1, out1) = matcher.SearchByProjection([empty, _through(pts, handle)])
+    assert n0 == 0 and len(out0) == 0
+    no, oo = _expected(pts)
+    assert n1 == no and np.array_equal(out1, oo)
+    D.close()
+
+
+# ---- 3. republish ------------------------------------------------------------------------------------------------------------------
+@gpu
+def test_republish_alternating_scenes_two_matchers(matcher):
+    from pointslot_amd.frame import DeviceFrame
+    from pointslot_amd.matcher import ORBmatcher
+    A = _scene(0x51070020)        # n = 2000
+    B = _scene(0x51070021)        # n = 600
+    m2 = ORBmatcher(0.8, True)
+    F = DeviceFrame(2000)
+    for rnd in range(3):
+        for sc in (A, B):
+            _publish_scene(F, sc[0])
+            for m in (matcher, m2):
+                res = m.SearchByProjection([_through(sc[0], F), _through(sc[1], F)])
+                for pr, (n, out) in zip(sc[:2], res):
+                    no, oo = _expected(pr)
+                    assert n == no and np.array_equal(out, oo), (rnd, pr["mode"])
+    got = F.read()
+    assert got["n"] == 600 and got["cell_idx"].max() < 600
+    # nothing of scene A is left behind the 600 keypoints of B: a larger publish that stays inside the grid's first cells would show it
+    F.publish({"x": np.zeros(0), "y": np.zeros(0), "octave": np.zeros(0), "angle": np.zeros(0)}, None, np.zeros((0, 32), np.uint8), (0, 0, 1, 1))
+    assert F.read()["n"] == 0 and not F.read()["cell_off"].any()
+    m2.close(); F.close()
+
+
+# ---- 4. from the extractor ---------------------------------------------------------------------------------------------------------
+@gpu
+def test_publish_from_the_extractor():
+    from pointslot_amd import synth
+    from pointslot_amd.extractor import ORBextractor, ComputeStereoMatches
+    from pointslot_amd.frame import DeviceFrame
+    from pointslot_amd.matcher import build_grid
+    bf, fx = 384.38148, 721.5377
+    mb, mbf = np.float32(bf / fx), np.float32(bf)
+    L, R = synth.stereo_pair(w=800, h=300)
+    grid = (np.float32(0), np.float32(0), np.float32(64) / np.float32(800), np.float32(48) / np.float32(300))
+
+    def check(F, kps, desc, ur):
+        got = F.read()
+        assert got["n"] == len(kps) > 300
+        assert np.array_equal(got["x"].view(np.uint32), kps["x"].view(np.uint32)) and np.array_equal(got["y"].view(np.uint32), kps["y"].view(np.uint32))
+        assert np.array_equal(got["octave"], kps["octave"]) and np.array_equal(got["angle"].view(np.uint32), kps["angle"].view(np.uint32))
+        assert np.array_equal(got["u_right"].view(np.uint32), ur.view(np.uint32)) and (ur >= 0).sum() > 100
+        assert np.array_equal(got["desc"], desc)
+        _assert_input_condition(kps["x"], kps["y"], grid)
+        off, idx = build_grid(kps["x"], kps["y"], *grid)
+        assert np.array_equal(got["cell_off"], off) and np.array_equal(got["cell_idx"][:len(idx)], idx) and not got["cell_idx"][len(idx):].any()
+
+    F = DeviceFrame(600)
+    # the batched layout: image 2k = left, 2k + 1 = right, pair k
+    ex = ORBextractor(500, 1.2, 8, 20, 5, max_batch=2)
+    ex.extract_batch([L, R])
+    ex.stereo_match_batch(1, mb, mbf)
+    (kps, desc, ur, _, _), = ex.stereo_fetch_frames(1)
+    F.publish_from(ex, 0, 0, len(kps), grid)
+    check(F, kps, desc, ur)
+    # the reference's layout: two extractor objects and ComputeStereoMatches; the left handle holds image 0 and pair 0
+    exl, exr = ORBextractor(500, 1.2, 8, 20, 5), ORBextractor(500, 1.2, 8, 20, 5)
+    kl, dl = exl(L); exr(R)
+    url, _ = ComputeStereoMatches(exl, exr, mb, mbf)
+    assert np.array_equal(kl.view(np.uint8), kps.view(np.uint8))
+    F.publish_from(exl, 0, 0, len(kl), grid)
+    check(F, kl, dl, url)
+    # without a pair: monocular
+    F.publish_from(exl, 0, -1, len(kl), grid)
+    assert np.all(F.read()["u_right"] == -1)
+    ex.close(); exl.close(); exr.close(); F.close()
+
+
+# ---- 5. fuse ---------------------------------------------------------------------------------------------------------------------------
+@gpu
+@pytest.mark.parametrize("seed,kw", [(41, {}), (43, {"box": (300, 600, 100, 300)})])
+def test_fuse_search_through_a_frame(matcher, handle, seed, kw):
+    import oracle_lib
+    from pointslot_amd import synth
+    from pointslot_amd.matcher import build_grid
+    pr = synth.fuse_scene(seed, **kw)
+    T = pr["train"]
+    T["cell_off"], T["cell_idx"] = build_grid(T["x"], T["y"], *T["grid"])
+    _assert_input_condition(T["x"], T["y"], T["grid"])
+    (hi, hd), = matcher.FuseSearch([pr])
+    handle.publish(dict(T, angle=np.zeros(len(T["x"]), np.float32)), T["u_right"], T["desc"], T["grid"])
+    (gi, gd), (gi2, gd2) = matcher.FuseSearch([dict(pr, train={"frame": handle}), pr])      # frame-backed next to host-backed
+    oi, od = oracle_lib.fuse_search(pr)
+    for a, b in ((gi, gd), (gi2, gd2), (hi, hd)):
+        assert np.array_equal(a, oi) and np.array_equal(b, od)
+    assert (gi >= 0).sum() > 50
+
+
+# ---- 6. errors -----------------------------------------------------------------------------------------------------------------------
+@gpu
+def test_frame_errors(matcher):
+    from pointslot_amd import _lib, synth
+    from pointslot_amd.extractor import ORBextractor
+    from pointslot_amd.frame import DeviceFrame
+    frame, pts, _, _ = _scene(0x51070021)          # n = 600
+    F = DeviceFrame(500)
+    with pytest.raises(_lib.PointslotError) as e:
+        _publish_scene(F, frame)
+    assert e.value.code == _lib.PS_ERR_CAPACITY
+    F.close()
+    F = DeviceFrame(700)
+    with pytest.raises(_lib.PointslotError) as e:   # never published
+        matcher.SearchByProjection([dict(pts, train={"frame": F, "occupied": np.zeros(0, np.uint8)})])
+    assert e.value.code == _lib.PS_ERR_INVALID and "never been published" in str(e.value)
+    _publish_scene(F, frame)
+    short = _through(pts, F)
+
+    class Fake:                                     # a handle that claims another count than the frame holds
+        _h = F._h
+        def __len__(self): return 599
+    short["train"] = {"frame": Fake(), "occupied": frame["train"]["occupied"][:599], "in_bbox": frame["train"]["in_bbox"][:599]}
+    with pytest.raises(_lib.PointslotError, match="train.n = 599, the frame handle holds 600") as e:
+        matcher.SearchByProjection([short])
+    assert e.value.code == _lib.PS_ERR_INVALID
+    # a wrong n handed to publish_from: the next search that consumes the frame reports it
+    L, _ = synth.stereo_pair(w=800, h=300)
+    ex = ORBextractor(500, 1.2, 8, 20, 5)
+    kps, desc = ex(L)
+    n = len(kps)
+    grid = (0.0, 0.0, 64.0 / 800.0, 48.0 / 300.0)
+    F.publish_from(ex, 0, -1, n + 5, grid)
+    sc = synth.projection_scene(3, n=n + 5, m=40)
+    bad = {"train": {"frame": F, "occupied": np.zeros(n + 5, np.uint8)}, "scale_factors": sc["scale_factors"], "mode": "points",
+           "query": sc["points_query"], "th": 1.0}
+    with pytest.raises(_lib.PointslotError, match="extractor's count differed") as e:
+        matcher.SearchByProjection([bad])
+    assert e.value.code == _lib.PS_ERR_INVALID
+    F.publish_from(ex, 0, -1, n, grid)              # ... and the right n clears it
+    good = dict(bad, train={"frame": F, "occupied": np.zeros(n, np.uint8)})
+    (nm, out), = matcher.SearchByProjection([good])
+    assert nm >= 0 and len(out) == n
+    ex.close(); F.close()
+
+
+# ---- 7. poisoned memory ------------------------------------------------------------------------------------------------------------
+@gpu
+def test_frame_slice_with_poisoned_device_memory():
+    """fresh slabs and arenas filled with 0xFF bytes (PS_DEBUG_FILL) instead of whatever the driver hands out"""
+    env = dict(os.environ, PS_DEBUG_FILL="255")
+    r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-m", "gpu", "-x", "-k", "test_publish_host_parity and 257 or test_republish",
+                        os.path.abspath(__file__)], capture_output=True, text=True, env=env, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
+    assert "2 passed" in r.stdout, r.stdout[-500:]
