@@ -378,6 +378,94 @@ int ps_frame_debug_read(ps_frame* f, int what, void* out, size_t out_bytes, int*
 int ps_search_by_projection_frames(ps_matcher* m, ps_proj_problem* probs, ps_frame* const* frames, int nprob);
 int ps_fuse_search_frames(ps_matcher* m, ps_fuse_problem* problems, ps_frame* const* frames, int nproblems);
 
+/* LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:414-707) for a batch of independent keyframes, each with its ordered
+ * neighbours: ORBmatcher::SearchForTriangulation (src/ORBmatcher.cc:783-979, called at LocalMapping.cc:496) against every
+ * neighbour, then the triangulation of every match and its gates (LocalMapping.cc:461-475, :519-684).
+ *
+ * ps_tri_keyframe is one KeyFrame as both halves read it: x, y, octave, angle = mvKeysUn; x_raw, y_raw = mvKeys[i].pt, which
+ * KeyFrame::UnprojectStereo reads (src/KeyFrame.cc:716-717; NULL = the same as x, y); u_right, depth = mvuRight, mvDepth
+ * (u_right >= 0 implies depth > 0); desc = mDescriptors rows; node[i] = the id of the mFeatVec node that lists feature i, -1
+ * for a feature in none; occupied[i] = GetMapPoint(i) != NULL; rcw (row-major), tcw, ow = GetRotation, GetTranslation,
+ * GetCameraCenter; fx .. mbf the members of that name; scale_factors, level_sigma2 = mvScaleFactors, mvLevelSigma2.
+ * f12[i] = ComputeF12(kf1, kf2[i]) row-major (LocalMapping.cc:804-823): host glue, the caller's.
+ *
+ * The winner rule.  The candidates of feature idx1 are the unoccupied features of the neighbour with the same node id (under
+ * only_stereo: the stereo ones), in ascending index - the order DBoW2::FeatureVector::addFeature builds.  vbMatched2
+ * (ORBmatcher.cc:803) is read at :852 and never written, so idx1's partner depends on no other feature, and one feature of the
+ * neighbour may be chosen by several.  No gate (:865-877: TH_LOW, the epipole disc for mono-mono pairs, CheckDistEpipolarLine
+ * :261-278) depends on bestDist, and `dist > bestDist` (:865) lets an equal distance replace the held one: the winner is the
+ * least distance <= 50 among the candidates that pass the gates, and among equal distances the HIGHEST index.
+ * check_orientation applies the 30-bin histogram and ComputeThreeMaxima (:890-936) to the matches of one neighbour.
+ *
+ * The chain rule.  The only state the reference carries from one neighbour to the next is pKF1->GetMapPoint(idx1) (:826-830),
+ * filled by mpCurrentKeyFrame->AddMapPoint(pMP, idx1) (LocalMapping.cc:693) when a match passes every gate.  With chain = 1
+ * neighbour i sees kf1.occupied OR "status 0 at an earlier neighbour": such a feature is skipped - status 2, no match, no
+ * histogram entry - which equals the reference's sequential loop.  chain = 0 serves every neighbour from kf1.occupied alone
+ * (SearchForTriangulation by itself).  CheckNewKeyFrames()'s early return (LocalMapping.cc:455) is not modelled, like the
+ * abort flag of ps_local_ba_batch.  pKF2->AddMapPoint (:694) fills a slot of a neighbour, which no later search of the same
+ * call reads as long as the neighbours are distinct keyframes.
+ *
+ * triangulate = 1 restates LocalMapping.cc:461-475 and :519-684 for a stereo / RGB-D system (!mbMonocular): a neighbour whose
+ * baseline is below its mb is skipped as a whole (status 11 everywhere, nmatches 0); otherwise every surviving match gets the
+ * rays and cosParallaxRays, cosParallaxStereo1 / 2 (the `if / else if` of :552-555), the three-way choice between linear
+ * triangulation, UnprojectStereo(idx1) and UnprojectStereo(idx2), the depth tests, the reprojection tests (5.991 / 7.8, with
+ * mpCurrentKeyFrame->mbf for both keyframes as written at :631, :658) and the distance-ratio test against ratio_factor
+ * (1.5f * mfScaleFactor).  Float expressions are evaluated as written; cv::Mat products, Mat::dot and cv::norm accumulate in
+ * double and round once.  Two modelling choices, where the reference's arithmetic is OpenCV- or libm-internal:
+ *   - the null vector: cv::SVD::compute on the 4 x 4 float matrix A (:576) becomes the right singular vector of the least
+ *     singular value computed in FP64 on the float entries of A (one-sided Jacobi); the division by its fourth component is
+ *     FP64, each coordinate is rounded to float once; "w == 0" tests the fourth component rounded to float;
+ *   - the cosine: cos(2 * atan2(mb / 2, depth)) (:553, :555) is evaluated in FP64 on the float mb / 2 and depth, rounded once.
+ *
+ * Outputs, per neighbour i and feature idx1 of keyframe 1 ([k][n1] row-major):
+ *   match    : idx2 or -1 - vMatches12 after the rotation check (and, with chain, without the skipped features)
+ *   nmatches : [k] the return value of SearchForTriangulation
+ *   status   : (triangulate) 0 point created, 1 no match, 2 the slot of keyframe 1 is occupied at this neighbour, 3 low
+ *              parallax (:595), 4 w == 0 (:580), 5 z1 <= 0, 6 z2 <= 0, 7 reprojection in keyframe 1, 8 reprojection in the
+ *              neighbour, 9 zero distance (:674), 10 scale ratio (:683), 11 neighbour skipped by the baseline gate
+ *   x3d      : (triangulate) [k][n1][3], the new point where status is 0
+ *   nnew     : points created over all neighbours (the reference's nnew)
+ * With triangulate = 0, x3d and status are not written and may be NULL.  What follows a created point - new MapPoint,
+ * AddObservation, AddMapPoint, ComputeDistinctiveDescriptors, UpdateNormalAndDepth, mlpRecentAddedMapPoints (:688-704) - is
+ * map surgery and stays with the caller, in (neighbour, idx1) order.
+ *
+ * Limits: n <= 8191 features per keyframe, k <= 32 neighbours.  A problem beyond them fails alone: its outputs are left
+ * untouched and the call returns PS_ERR_CAPACITY after serving the others.  n1 == 0, k == 0 and a neighbour with n == 0 are
+ * valid and give empty results.  A node may hold any number of features. */
+typedef struct ps_tri_keyframe {
+  int32_t n;
+  const float* x; const float* y;
+  const float* x_raw; const float* y_raw;
+  const int32_t* octave; const float* angle;
+  const float* u_right; const float* depth;
+  const uint8_t* desc;                 /* [n][32] */
+  const int32_t* node;
+  const uint8_t* occupied;
+  float rcw[9], tcw[3], ow[3];
+  float fx, fy, cx, cy, invfx, invfy, mb, mbf;
+  float scale_factors[8], level_sigma2[8];
+} ps_tri_keyframe;
+typedef struct ps_tri_problem {
+  ps_tri_keyframe kf1;                 /* mpCurrentKeyFrame */
+  int32_t k;                           /* neighbours, in vpNeighKFs order */
+  const ps_tri_keyframe* kf2;          /* [k] */
+  const float* f12;                    /* [k][9] */
+  int32_t only_stereo, check_orientation, triangulate, chain;
+  float ratio_factor;
+  int32_t* match;                      /* out [k][n1] */
+  int32_t* nmatches;                   /* out [k] */
+  float* x3d;                          /* out [k][n1][3] */
+  uint8_t* status;                     /* out [k][n1] */
+  int32_t* nnew;                       /* out, one value */
+} ps_tri_problem;
+int ps_create_new_map_points(ps_matcher* m, ps_tri_problem* probs, int nprob);
+/* ... with x, y, octave, angle, u_right and desc of keyframe 1 of problem p taken from kf1_frames[p] where that is non-null
+ * (those six may then be NULL; x_raw / y_raw = NULL means the handle's x, y).  node, occupied, depth and the pose stay host
+ * fields: they change from call to call.  kf1.n must equal the handle's count (else PS_ERR_INVALID); ordering and lifetimes
+ * are those of ps_search_by_projection_frames.  The current keyframe is read once per neighbour, so it is published once and
+ * read k times. */
+int ps_create_new_map_points_frames(ps_matcher* m, ps_tri_problem* probs, ps_frame* const* kf1_frames, int nprob);
+
 
 /* ------------------------------------------------------------------------------------------------
  * Optimiser — replaces the hot static members of ORB_SLAM2::Optimizer

@@ -132,7 +132,7 @@ extern "C" __global__ __launch_bounds__(256) void frame_stage(const FrameStageJo
   const size_t t0 = (size_t)J.t_off;
   for (int i = tid; i < n; i += nth) {
     D.tx[t0 + i] = S.x[i]; D.ty[t0 + i] = S.y[i]; D.toct[t0 + i] = S.octave[i]; D.tur[t0 + i] = S.u_right[i];
-    D.cell_idx[t0 + i] = S.cell_idx[i];
+    if (D.cell_idx) D.cell_idx[t0 + i] = S.cell_idx[i];
     if (D.tang) D.tang[t0 + i] = S.angle[i];
   }
   {
@@ -140,7 +140,8 @@ extern "C" __global__ __launch_bounds__(256) void frame_stage(const FrameStageJo
     uint4* dd = reinterpret_cast<uint4*>(D.tdesc + t0 * 32);
     for (int k = tid; k < 2 * n; k += nth) dd[k] = sd[k];
   }
-  for (int i = tid; i <= PS_FRAME_NCELL; i += nth) D.cell_off[(size_t)J.grid_off + i] = S.cell_off[i];
+  if (D.cell_off)
+    for (int i = tid; i <= PS_FRAME_NCELL; i += nth) D.cell_off[(size_t)J.grid_off + i] = S.cell_off[i];
   if (tid == 0) D.status[J.prob] = (S.hdr->n != n || S.hdr->mismatch) ? 1 : 0;
 }
 

@@ -44,6 +44,6 @@ struct FrameStageJob {
 };
 struct FrameStageDst {
   float* tx; float* ty; int32_t* toct; float* tang; float* tur; uint8_t* tdesc;   // tang may be nullptr (the fuse search has none)
-  int32_t* cell_off; int32_t* cell_idx;
+  int32_t* cell_off; int32_t* cell_idx;                                           // both may be nullptr (a consumer without the grid: tri_match)
   int32_t* status;                    // per problem: non-zero where the slab does not hold the frame the caller described
 };

@@ -10,6 +10,7 @@
 #include <vector>
 #include "frame_host.h"
 #include "match_plan.h"
+#include "tri_plan.h"
 #include "ps_common.h"
 
 extern "C" {
@@ -20,6 +21,7 @@ void psk_pj_launch(const PjArrays*, int, int, int, int, int, hipStream_t);
 void psk_fuse_launch(const FuArrays*, int, int, hipStream_t);
 void psk_distinctive_launch(const uint8_t*, const int32_t*, int32_t*, int, hipStream_t);
 void psk_frame_stage_launch(const FrameStageJob*, int, const FrameStageDst*, hipStream_t);
+void psk_tri_launch(const TriArrays*, int, int, int, hipStream_t);
 }
 
 struct ps_matcher {
@@ -32,7 +34,7 @@ struct ps_matcher {
   size_t h_bytes = 0;
   uint8_t* d_wide = nullptr;  // second arena, only for the wide re-run of search problems whose windows overflowed the candidate store
   size_t d_wide_bytes = 0;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;   // around the kernels of the last brute-force / projection call (ps_matcher_last_kernel_ms)
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;   // around the kernels of the last brute-force / projection / triangulation call (ps_matcher_last_kernel_ms)
   float last_kernel_ms = 0;
 };
 
@@ -615,6 +617,225 @@ int ps_fuse_search(ps_matcher* m, ps_fuse_problem* probs, int nprob) { return fu
 
 int ps_fuse_search_frames(ps_matcher* m, ps_fuse_problem* probs, ps_frame* const* frames, int nprob) {
   return fuse_search(m, probs, frames, nprob);
+}
+
+
+// ---- LocalMapping::CreateNewMapPoints: SearchForTriangulation against every neighbour + the triangulation gates ----
+namespace {
+// the host pointers one keyframe of a triangulation problem needs (on_device: x .. desc come from a frame handle)
+bool tri_keyframe_ok(const ps_tri_keyframe& K, bool on_device) {
+  if (K.n <= 0) return K.n == 0;
+  if (!K.depth || !K.node || !K.occupied) return false;
+  if ((K.x_raw == nullptr) != (K.y_raw == nullptr)) return false;
+  return on_device || (K.x && K.y && K.octave && K.angle && K.u_right && K.desc);
+}
+void tri_fill_kf(TriKf& d, const ps_tri_keyframe& K, int32_t f_off, int32_t raw_off) {
+  memset(&d, 0, sizeof(d));
+  d.f_off = f_off; d.n = K.n; d.raw_off = raw_off;
+  memcpy(d.rcw, K.rcw, 36); memcpy(d.tcw, K.tcw, 12); memcpy(d.ow, K.ow, 12);
+  d.fx = K.fx; d.fy = K.fy; d.cx = K.cx; d.cy = K.cy; d.invfx = K.invfx; d.invfy = K.invfy; d.mb = K.mb; d.mbf = K.mbf;
+  memcpy(d.scale, K.scale_factors, 32); memcpy(d.sigma2, K.level_sigma2, 32);
+}
+struct TriOff { size_t x, y, oct, ang, ur, depth, xraw, yraw, desc, occ; };
+// the feature arrays of one keyframe into its slices of the staging buffer (skip_keys: x .. desc are staged on the device)
+void tri_pack_kf(uint8_t* H, const TriOff& o, const ps_tri_keyframe& K, const TriKf& d, bool skip_keys) {
+  const size_t n = (size_t)K.n, f = (size_t)d.f_off;
+  if (n == 0) return;
+  if (!skip_keys) {
+    memcpy(H + o.x + f * 4, K.x, n * 4); memcpy(H + o.y + f * 4, K.y, n * 4); memcpy(H + o.oct + f * 4, K.octave, n * 4);
+    memcpy(H + o.ang + f * 4, K.angle, n * 4); memcpy(H + o.ur + f * 4, K.u_right, n * 4); memcpy(H + o.desc + f * 32, K.desc, n * 32);
+  }
+  memcpy(H + o.depth + f * 4, K.depth, n * 4); memcpy(H + o.occ + f, K.occupied, n);
+  if (d.raw_off >= 0) { memcpy(H + o.xraw + (size_t)d.raw_off * 4, K.x_raw, n * 4); memcpy(H + o.yraw + (size_t)d.raw_off * 4, K.y_raw, n * 4); }
+}
+}  // namespace
+
+static int create_new_map_points(ps_matcher* m, ps_tri_problem* probs, ps_frame* const* frames, int nprob) {
+  if (!m || !probs || nprob < 1) return ps_set_error(PS_ERR_INVALID, "ps_create_new_map_points: bad argument");
+  std::lock_guard<std::mutex> lock(m->mu);
+  PS_HIP(hipSetDevice(m->device));
+  FrameUse U;
+  int frc = frame_use_init(U, m, frames, nprob, "triangulation");
+  if (frc != PS_OK) return frc;
+  std::vector<int> served, failed;
+  for (int p = 0; p < nprob; p++) {
+    const ps_tri_problem& P = probs[p];
+    if (P.kf1.n < 0 || P.k < 0 || (P.k > 0 && (!P.kf2 || !P.f12 || !P.nmatches)) || !P.nnew)
+      return ps_set_error(PS_ERR_INVALID, "triangulation problem %d: bad sizes or null pointers", p);
+    bool beyond = P.kf1.n > PS_TRI_MAX_N || P.k > PS_TRI_MAX_K;
+    for (int i = 0; i < P.k && i < PS_TRI_MAX_K; i++) {
+      if (P.kf2[i].n < 0) return ps_set_error(PS_ERR_INVALID, "triangulation problem %d: neighbour %d has a negative count", p, i);
+      beyond = beyond || P.kf2[i].n > PS_TRI_MAX_N;
+    }
+    if (beyond) { failed.push_back(p); continue; }
+    if (!tri_keyframe_ok(P.kf1, U.of[p] != nullptr)) return ps_set_error(PS_ERR_INVALID, "triangulation problem %d: null arrays in keyframe 1", p);
+    for (int i = 0; i < P.k; i++)
+      if (!tri_keyframe_ok(P.kf2[i], false)) return ps_set_error(PS_ERR_INVALID, "triangulation problem %d: null arrays in neighbour %d", p, i);
+    if (P.k > 0 && P.kf1.n > 0 && (!P.match || (P.triangulate && (!P.x3d || !P.status))))
+      return ps_set_error(PS_ERR_INVALID, "triangulation problem %d: null output arrays", p);
+    if (U.of[p] && (frc = frame_use_check(U, p, P.kf1.n, "triangulation")) != PS_OK) return frc;
+    served.push_back(p);
+  }
+  const int ns = (int)served.size();
+  if (ns == 0)
+    return ps_set_error(PS_ERR_CAPACITY, "triangulation problem %d (and %zu more): more than %d features in a keyframe or more than %d neighbours", failed[0],
+                        failed.size() - 1, PS_TRI_MAX_N, PS_TRI_MAX_K);
+  // the distinct nodes of every keyframe 1 (sorted): a feature's node becomes its index among them, a neighbour's features are
+  // bucketed by that index
+  std::vector<std::vector<int32_t>> nodes(ns);
+  ps_parallel_for(ns, (size_t)ns << 16, [&](int s) {
+    const ps_tri_keyframe& K = probs[served[s]].kf1;
+    std::vector<int32_t>& un = nodes[s];
+    for (int i = 0; i < K.n; i++) if (K.node[i] >= 0) un.push_back(K.node[i]);
+    std::sort(un.begin(), un.end());
+    un.erase(std::unique(un.begin(), un.end()), un.end());
+  });
+  std::vector<TriProb> hp(ns);
+  std::vector<int32_t> kf_first(ns);
+  size_t NF = 0, NR = 0, NO = 0, NN = 0, npairs = 0, nkf = 0;
+  int max_n1 = 0, any_tri = 0;
+  for (int s = 0; s < ns; s++) {
+    const ps_tri_problem& P = probs[served[s]];
+    TriProb& d = hp[s];
+    memset(&d, 0, sizeof(d));
+    d.kf1 = (int32_t)nkf; d.first_pair = (int32_t)npairs; d.k = P.k; d.n1 = P.kf1.n;
+    d.only_stereo = P.only_stereo; d.check_ori = P.check_orientation; d.triangulate = P.triangulate; d.chain = P.chain;
+    d.ratio_factor = P.ratio_factor;
+    kf_first[s] = (int32_t)nkf;
+    nkf += 1 + (size_t)P.k; npairs += (size_t)P.k;
+    max_n1 = std::max(max_n1, P.kf1.n);
+    any_tri |= P.triangulate ? 1 : 0;
+  }
+  std::vector<TriKf> hk(nkf);
+  std::vector<TriPair> hr(npairs);
+  for (int s = 0; s < ns; s++) {
+    const ps_tri_problem& P = probs[served[s]];
+    for (int i = -1; i < P.k; i++) {
+      const ps_tri_keyframe& K = i < 0 ? P.kf1 : P.kf2[i];
+      const bool raw = K.n > 0 && K.x_raw != nullptr;
+      tri_fill_kf(hk[(size_t)kf_first[s] + 1 + i], K, (int32_t)NF, raw ? (int32_t)NR : -1);
+      NF += (size_t)K.n;
+      if (raw) NR += (size_t)K.n;
+      if (i >= 0) {
+        TriPair& r = hr[(size_t)hp[s].first_pair + i];
+        memset(&r, 0, sizeof(r));
+        r.prob = s; r.kf2 = kf_first[s] + 1 + i; r.node_off = (int32_t)NN; r.out_off = (int32_t)NO;
+        memcpy(r.f12, P.f12 + 9 * (size_t)i, 36);
+        NN += nodes[s].size() + 1; NO += (size_t)P.kf1.n;
+      }
+    }
+  }
+  if (NF > 0x7FFFFFFFull || NO > 0x7FFFFFFFull || NN > 0x7FFFFFFFull) return ps_set_error(PS_ERR_CAPACITY, "ps_create_new_map_points: the batch holds more than 2^31 features");
+  size_t off = 0;
+  auto take = [&](size_t bytes) { size_t r = off; off += al(bytes + 64); return r; };
+  const size_t o_prob = take(sizeof(TriProb) * ns), o_pair = take(sizeof(TriPair) * npairs), o_kf = take(sizeof(TriKf) * nkf);
+  TriOff O;
+  O.x = take(NF * 4); O.y = take(NF * 4); O.oct = take(NF * 4); O.ang = take(NF * 4); O.ur = take(NF * 4); O.depth = take(NF * 4);
+  O.xraw = take(NR * 4); O.yraw = take(NR * 4); O.desc = take(NF * 32); O.occ = take(NF);
+  const size_t o_aux = take(NF * 4), o_noff = take(NN * 4);
+  const size_t o_jobs = U.any() ? take(sizeof(FrameStageJob) * ns) : 0;
+  const size_t in_bytes = off;
+  const size_t o_match = take(NO * 4), o_nm = take(npairs * 4), o_nnew = take((size_t)ns * 4);
+  const size_t o_fst = U.any() ? take((size_t)ns * 4) : 0;
+  const size_t o_status = take(any_tri ? NO : 0), o_x3d = take(any_tri ? NO * 12 : 0);
+  const size_t out_end = off;
+  int rc = ensure(m, off);
+  if (rc != PS_OK) return rc;
+  uint8_t* H = m->h_buf;
+  memcpy(H + o_prob, hp.data(), sizeof(TriProb) * ns);
+  if (npairs) memcpy(H + o_pair, hr.data(), sizeof(TriPair) * npairs);
+  memcpy(H + o_kf, hk.data(), sizeof(TriKf) * nkf);
+  if (U.any()) {
+    for (int s = 0; s < ns; s++)
+      if (U.of[served[s]] && hp[s].n1 > 0 && hp[s].k > 0)
+        U.jobs.push_back(FrameStageJob{U.of[served[s]]->slab, hp[s].n1, hk[(size_t)kf_first[s]].f_off, 0, s});
+    memset(H + o_jobs, 0, sizeof(FrameStageJob) * ns);
+    if (!U.jobs.empty()) memcpy(H + o_jobs, U.jobs.data(), sizeof(FrameStageJob) * U.jobs.size());
+  }
+  // every problem fills exactly its own slices of the staging buffer
+  ps_parallel_for(ns, in_bytes, [&](int s) {
+    const ps_tri_problem& P = probs[served[s]];
+    const std::vector<int32_t>& un = nodes[s];
+    const int nu = (int)un.size();
+    const TriKf& d1 = hk[(size_t)kf_first[s]];
+    tri_pack_kf(H, O, P.kf1, d1, U.of[served[s]] != nullptr);
+    int32_t* aux1 = (int32_t*)(H + o_aux) + d1.f_off;
+    for (int i = 0; i < P.kf1.n; i++) {
+      const int32_t v = P.kf1.node[i];
+      aux1[i] = v < 0 ? -1 : (int32_t)(std::lower_bound(un.begin(), un.end(), v) - un.begin());
+    }
+    std::vector<int32_t> slot(nu + 1), where;
+    for (int i = 0; i < P.k; i++) {
+      const ps_tri_keyframe& K = P.kf2[i];
+      const TriKf& d2 = hk[(size_t)kf_first[s] + 1 + i];
+      tri_pack_kf(H, O, K, d2, false);
+      // the neighbour's features bucketed by keyframe 1's nodes: a counting sort, stable in the feature index
+      int32_t* noff = (int32_t*)(H + o_noff) + hr[(size_t)hp[s].first_pair + i].node_off;
+      int32_t* aux2 = (int32_t*)(H + o_aux) + d2.f_off;
+      where.assign((size_t)K.n, -1);
+      std::fill(slot.begin(), slot.end(), 0);
+      for (int j = 0; j < K.n; j++) {
+        const int32_t v = K.node[j];
+        if (v < 0) continue;
+        const auto it = std::lower_bound(un.begin(), un.end(), v);
+        if (it == un.end() || *it != v) continue;
+        where[j] = (int32_t)(it - un.begin());
+        slot[where[j] + 1]++;
+      }
+      for (int c = 0; c < nu; c++) slot[c + 1] += slot[c];
+      memcpy(noff, slot.data(), (size_t)(nu + 1) * 4);
+      const int32_t filled = slot[nu];
+      for (int j = 0; j < K.n; j++)
+        if (where[j] >= 0) aux2[slot[where[j]]++] = j;
+      for (int j = filled; j < K.n; j++) aux2[j] = 0;
+    }
+  });
+  uint8_t* D = m->d_buf;
+  PS_HIP(hipMemcpyAsync(D, H, in_bytes, hipMemcpyHostToDevice, m->stream));
+  hipEventRecord(m->ev0, m->stream);   // (the staging copy of frame-backed keyframes counts as kernel time of the call)
+  if (U.any()) {
+    FrameStageDst dst{(float*)(D + O.x), (float*)(D + O.y), (int32_t*)(D + O.oct), (float*)(D + O.ang), (float*)(D + O.ur), D + O.desc,
+                      nullptr, nullptr, (int32_t*)(D + o_fst)};
+    PS_HIP(hipMemsetAsync(D + o_fst, 0, (size_t)ns * 4, m->stream));
+    if ((frc = frame_use_stage(U, m, (const FrameStageJob*)(D + o_jobs), dst)) != PS_OK) return frc;
+  }
+  TriArrays A;
+  A.prob = (const TriProb*)(D + o_prob); A.pair = (const TriPair*)(D + o_pair); A.kf = (const TriKf*)(D + o_kf);
+  A.x = (const float*)(D + O.x); A.y = (const float*)(D + O.y); A.oct = (const int32_t*)(D + O.oct); A.ang = (const float*)(D + O.ang);
+  A.ur = (const float*)(D + O.ur); A.depth = (const float*)(D + O.depth); A.xraw = (const float*)(D + O.xraw); A.yraw = (const float*)(D + O.yraw);
+  A.desc = D + O.desc; A.occ = D + O.occ; A.aux = (const int32_t*)(D + o_aux); A.node_off = (const int32_t*)(D + o_noff);
+  A.match = (int32_t*)(D + o_match); A.nmatch = (int32_t*)(D + o_nm); A.x3d = (float*)(D + o_x3d); A.status = D + o_status; A.nnew = (int32_t*)(D + o_nnew);
+  psk_tri_launch(&A, ns, (int)npairs, max_n1, m->stream);
+  hipEventRecord(m->ev1, m->stream);
+  PS_HIP(hipGetLastError());
+  PS_HIP(hipMemcpyAsync(H + o_match, D + o_match, out_end - o_match, hipMemcpyDeviceToHost, m->stream));
+  PS_HIP(hipStreamSynchronize(m->stream));
+  hipEventElapsedTime(&m->last_kernel_ms, m->ev0, m->ev1);
+  int stale = -1;
+  for (int s = 0; s < ns; s++) {
+    ps_tri_problem& P = probs[served[s]];
+    if (U.any() && ((const int32_t*)(H + o_fst))[s]) { stale = stale < 0 ? served[s] : stale; continue; }   // its outputs stay as the caller left them
+    *P.nnew = ((const int32_t*)(H + o_nnew))[s];
+    if (P.k == 0) continue;
+    memcpy(P.nmatches, H + o_nm + (size_t)hp[s].first_pair * 4, (size_t)P.k * 4);
+    const size_t o0 = (size_t)hr[(size_t)hp[s].first_pair].out_off, cnt = (size_t)P.k * (size_t)P.kf1.n;
+    if (cnt == 0) continue;
+    memcpy(P.match, H + o_match + o0 * 4, cnt * 4);
+    if (P.triangulate) { memcpy(P.status, H + o_status + o0, cnt); memcpy(P.x3d, H + o_x3d + o0 * 12, cnt * 12); }
+  }
+  if (stale >= 0)
+    return ps_set_error(PS_ERR_INVALID, "triangulation problem %d: the frame handle does not hold the %d keypoints it was published with "
+                        "(the extractor's count differed from the n given to ps_frame_publish_orb)", stale, probs[stale].kf1.n);
+  if (!failed.empty())
+    return ps_set_error(PS_ERR_CAPACITY, "triangulation problem %d (and %zu more): more than %d features in a keyframe or more than %d neighbours", failed[0],
+                        failed.size() - 1, PS_TRI_MAX_N, PS_TRI_MAX_K);
+  return PS_OK;
+}
+
+int ps_create_new_map_points(ps_matcher* m, ps_tri_problem* probs, int nprob) { return create_new_map_points(m, probs, nullptr, nprob); }
+
+int ps_create_new_map_points_frames(ps_matcher* m, ps_tri_problem* probs, ps_frame* const* kf1_frames, int nprob) {
+  return create_new_map_points(m, probs, kf1_frames, nprob);
 }
 
 }  // extern "C"

@@ -92,6 +92,16 @@ class ORBmatcher {
     if (n <= 0) return;
     if ((frames ? ps_fuse_search_frames(h_, p, frames, n) : ps_fuse_search(h_, p, n)) != PS_OK) throw std::runtime_error(ps_last_error());
   }
+  // LocalMapping::CreateNewMapPoints on caller-filled problems (include/pointslot_hip.h: ps_tri_problem): SearchForTriangulation
+  // against every neighbour and the triangulation gates.  kf1_frames: nullptr, or per problem the frame handle keyframe 1's keys
+  // and descriptors come from.  Returns the points created over all problems.
+  int CreateNewMapPoints(ps_tri_problem* p, ps_frame* const* kf1_frames, int n) {
+    if (n <= 0) return 0;
+    if ((kf1_frames ? ps_create_new_map_points_frames(h_, p, kf1_frames, n) : ps_create_new_map_points(h_, p, n)) != PS_OK) throw std::runtime_error(ps_last_error());
+    int total = 0;
+    for (int i = 0; i < n; i++) total += *p[i].nnew;
+    return total;
+  }
   ps_matcher* handle() { return h_; }   // (kernel time of the last call: ps_matcher_last_kernel_ms)
   static float RadiusByViewingCos(const float& viewCos) { return viewCos > 0.998 ? 2.5f : 4.0f; }   // ORBmatcher.cc:252-258
 
@@ -201,7 +211,72 @@ class ORBmatcher {
     return n;
   }
 
+  // int SearchForTriangulation(KeyFrame *pKF1, KeyFrame *pKF2, cv::Mat F12, vector<pair<size_t,size_t>> &vMatchedPairs,
+  //                            const bool bOnlyStereo)                                                                     :783-979
+  // over a KeyFrame-shaped type (KeyFrame.h: N, mvKeys, mvKeysUn, mvuRight, mvDepth, mDescriptors, mFeatVec, GetMapPoint,
+  // GetRotation, GetTranslation, GetCameraCenter, fx .. invfy, mb, mbf, mvScaleFactors, mvLevelSigma2; tests/cpp/keyframe_view.h).
+  // The node of a feature comes from walking the caller's mFeatVec.  A type with a non-null `ps_frame* mpDeviceFrame` has the keys
+  // and descriptors of pKF1 on the device already.
+  template <class KeyFrameT, class MatT>
+  int SearchForTriangulation(KeyFrameT* pKF1, KeyFrameT* pKF2, MatT F12, std::vector<std::pair<std::size_t, std::size_t>>& vMatchedPairs,
+                             const bool bOnlyStereo) {
+    TriSide S1, S2;
+    ps_frame* frame = deviceFrameOf(*pKF1);
+    ps_tri_problem p = ps_tri_problem{};
+    fillTriSide(S1, *pKF1, p.kf1, frame != nullptr);
+    ps_tri_keyframe k2 = ps_tri_keyframe{};
+    fillTriSide(S2, *pKF2, k2, false);
+    float f12[9];
+    for (int r = 0; r < 3; r++)
+      for (int c = 0; c < 3; c++) f12[3 * r + c] = F12.template at<float>(r, c);
+    std::vector<int32_t> match((std::size_t)std::max(p.kf1.n, 1), -1);
+    int32_t nmatches = 0, nnew = 0;
+    p.k = 1; p.kf2 = &k2; p.f12 = f12;
+    p.only_stereo = bOnlyStereo ? 1 : 0; p.check_orientation = mbCheckOrientation ? 1 : 0; p.triangulate = 0; p.chain = 0;
+    p.match = match.data(); p.nmatches = &nmatches; p.nnew = &nnew;
+    CreateNewMapPoints(&p, frame ? &frame : nullptr, 1);
+    vMatchedPairs.clear();
+    vMatchedPairs.reserve(nmatches);
+    for (int i = 0; i < p.kf1.n; i++)
+      if (match[i] >= 0) vMatchedPairs.push_back(std::make_pair((std::size_t)i, (std::size_t)match[i]));
+    return nmatches;
+  }
+
  protected:
+  // one KeyFrame as ps_tri_keyframe's arrays
+  struct TriSide {
+    std::vector<float> x, y, xr, yr, angle, ur, depth;
+    std::vector<int32_t> octave, node;
+    std::vector<uint8_t> desc, occupied;
+  };
+  template <class KeyFrameT>
+  static void fillTriSide(TriSide& S, KeyFrameT& KF, ps_tri_keyframe& k, bool on_device) {
+    const int n = KF.N, m = std::max(n, 1);
+    S.x.resize(m); S.y.resize(m); S.xr.resize(m); S.yr.resize(m); S.angle.resize(m); S.ur.resize(m); S.depth.resize(m); S.octave.resize(m);
+    S.node.assign(m, -1); S.occupied.assign(m, 0);
+    for (int i = 0; i < n; i++) {
+      S.x[i] = KF.mvKeysUn[i].pt.x; S.y[i] = KF.mvKeysUn[i].pt.y; S.octave[i] = KF.mvKeysUn[i].octave; S.angle[i] = KF.mvKeysUn[i].angle;
+      S.xr[i] = KF.mvKeys[i].pt.x; S.yr[i] = KF.mvKeys[i].pt.y; S.ur[i] = KF.mvuRight[i]; S.depth[i] = KF.mvDepth[i];
+      S.occupied[i] = KF.GetMapPoint(i) ? 1 : 0;
+    }
+    for (const auto& nodeAndFeatures : KF.mFeatVec)
+      for (const auto i : nodeAndFeatures.second)
+        if ((std::size_t)i < (std::size_t)n) S.node[i] = (int32_t)nodeAndFeatures.first;
+    S.desc = rows32(KF.mDescriptors, n);
+    k.n = n;
+    if (!on_device) { k.x = S.x.data(); k.y = S.y.data(); k.octave = S.octave.data(); k.angle = S.angle.data(); k.u_right = S.ur.data(); k.desc = S.desc.data(); }
+    k.x_raw = S.xr.data(); k.y_raw = S.yr.data(); k.depth = S.depth.data(); k.node = S.node.data(); k.occupied = S.occupied.data();
+    const auto R = KF.GetRotation(), t = KF.GetTranslation(), O = KF.GetCameraCenter();
+    for (int r = 0; r < 3; r++) {
+      for (int c = 0; c < 3; c++) k.rcw[3 * r + c] = R.template at<float>(r, c);
+      k.tcw[r] = t.template at<float>(r); k.ow[r] = O.template at<float>(r);
+    }
+    k.fx = KF.fx; k.fy = KF.fy; k.cx = KF.cx; k.cy = KF.cy; k.invfx = KF.invfx; k.invfy = KF.invfy; k.mb = KF.mb; k.mbf = KF.mbf;
+    for (int l = 0; l < 8; l++) {
+      k.scale_factors[l] = l < (int)KF.mvScaleFactors.size() ? KF.mvScaleFactors[l] : 1.f;
+      k.level_sigma2[l] = l < (int)KF.mvLevelSigma2.size() ? KF.mvLevelSigma2[l] : 1.f;
+    }
+  }
   // the "train" half of a windowed search: mvKeysUn-like keys, mvuRight, descriptors and the 64 x 48 grid of the frame (or of
   // one of its objects) as the arrays of ps_proj_train
   struct TrainSide {

@@ -312,3 +312,118 @@ def _fuse_search(self, problems):
 
 
 ORBmatcher.FuseSearch = _fuse_search
+
+
+# ---- LocalMapping::CreateNewMapPoints: SearchForTriangulation + triangulation (ps_create_new_map_points) ----------------
+class _TriKeyframe(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_int32), ("x", ctypes.c_void_p), ("y", ctypes.c_void_p), ("x_raw", ctypes.c_void_p), ("y_raw", ctypes.c_void_p),
+                ("octave", ctypes.c_void_p), ("angle", ctypes.c_void_p), ("u_right", ctypes.c_void_p), ("depth", ctypes.c_void_p),
+                ("desc", ctypes.c_void_p), ("node", ctypes.c_void_p), ("occupied", ctypes.c_void_p),
+                ("rcw", ctypes.c_float * 9), ("tcw", ctypes.c_float * 3), ("ow", ctypes.c_float * 3),
+                ("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float),
+                ("invfx", ctypes.c_float), ("invfy", ctypes.c_float), ("mb", ctypes.c_float), ("mbf", ctypes.c_float),
+                ("scale_factors", ctypes.c_float * 8), ("level_sigma2", ctypes.c_float * 8)]
+
+
+class _TriProblem(ctypes.Structure):
+    _fields_ = [("kf1", _TriKeyframe), ("k", ctypes.c_int32), ("kf2", ctypes.POINTER(_TriKeyframe)), ("f12", ctypes.c_void_p),
+                ("only_stereo", ctypes.c_int32), ("check_orientation", ctypes.c_int32), ("triangulate", ctypes.c_int32),
+                ("chain", ctypes.c_int32), ("ratio_factor", ctypes.c_float), ("match", ctypes.c_void_p), ("nmatches", ctypes.c_void_p),
+                ("x3d", ctypes.c_void_p), ("status", ctypes.c_void_p), ("nnew", ctypes.c_void_p)]
+
+
+TRI_STATUS = ("created", "no match", "slot occupied", "low parallax", "w == 0", "z1 <= 0", "z2 <= 0", "reprojection 1", "reprojection 2",
+              "zero distance", "scale ratio", "neighbour skipped")
+_TRI_KEYS = (("x", np.float32), ("y", np.float32), ("octave", np.int32), ("angle", np.float32), ("u_right", np.float32))
+
+
+def _fill_tri_keyframe(c, kf, keep, frame=None):
+    """one ps_tri_keyframe from a keyframe dict: x, y, octave, angle, u_right, depth, desc, node, occupied (x_raw, y_raw optional),
+    R (GetRotation), t (GetTranslation), ow (GetCameraCenter), K8 = (fx, fy, cx, cy, invfx, invfy, mb, mbf), scale_factors, level_sigma2.
+    frame: the DeviceFrame that holds x .. desc (keyframe 1 only); the dict then needs only n-sized depth, node, occupied."""
+    a = dict(depth=_arr(kf["depth"], np.float32), node=_arr(kf["node"], np.int32), occupied=_arr(kf["occupied"], np.uint8))
+    n = len(a["node"])
+    if frame is None:
+        a.update({k: _arr(kf[k], dt) for k, dt in _TRI_KEYS})
+        a["desc"] = _arr(kf["desc"], np.uint8).reshape(-1, 32)
+    if kf.get("x_raw") is not None:
+        a.update(x_raw=_arr(kf["x_raw"], np.float32), y_raw=_arr(kf["y_raw"], np.float32))
+    if any(len(v) != n for v in a.values()):
+        raise ValueError("the arrays of a keyframe differ in length")
+    keep.append(a)
+    c.n = n
+    for k, v in a.items():
+        setattr(c, k, v.ctypes.data)
+    c.rcw = (ctypes.c_float * 9)(*np.asarray(kf["R"], np.float32).reshape(9))
+    c.tcw = (ctypes.c_float * 3)(*np.asarray(kf["t"], np.float32).reshape(3))
+    c.ow = (ctypes.c_float * 3)(*np.asarray(kf["ow"], np.float32).reshape(3))
+    c.fx, c.fy, c.cx, c.cy, c.invfx, c.invfy, c.mb, c.mbf = [float(v) for v in kf["K8"]]
+    c.scale_factors = (ctypes.c_float * 8)(*np.asarray(kf["scale_factors"], np.float32))
+    c.level_sigma2 = (ctypes.c_float * 8)(*np.asarray(kf["level_sigma2"], np.float32))
+    return n
+
+
+lib.ps_create_new_map_points.argtypes = [ctypes.c_void_p, ctypes.POINTER(_TriProblem), ctypes.c_int]
+lib.ps_create_new_map_points_frames.argtypes = [ctypes.c_void_p, ctypes.POINTER(_TriProblem), ctypes.POINTER(ctypes.c_void_p), ctypes.c_int]
+
+
+def _create_new_map_points(self, problems, partial_ok=False):
+    """LocalMapping::CreateNewMapPoints for a batch of keyframes.  problems: list of dicts {kf1, kf2: [neighbours in order],
+    f12: [k, 3, 3] ComputeF12(kf1, kf2[i]), only_stereo, check_orientation (default: the matcher's), triangulate (default 1),
+    chain (default 1), ratio_factor (1.5f * mfScaleFactor)}; keyframe dicts as in _fill_tri_keyframe, and kf1 may carry
+    "frame" = a DeviceFrame holding its keys and descriptors.  Returns per problem a dict: match int32 [k, n1] (idx2 or -1),
+    nmatches int32 [k], status uint8 [k, n1] and x3d float32 [k, n1, 3] (triangulate), nnew; "failed" = True for a problem beyond
+    the limits when partial_ok lets the call return after PS_ERR_CAPACITY."""
+    n = len(problems)
+    arr = (_TriProblem * n)()
+    keep, outs, frames = [], [], []
+    for i, pr in enumerate(problems):
+        p = arr[i]
+        fr = pr["kf1"].get("frame")
+        frames.append(fr)
+        n1 = _fill_tri_keyframe(p.kf1, pr["kf1"], keep, fr)
+        k = len(pr["kf2"])
+        nb = (_TriKeyframe * max(k, 1))()
+        for j, kf in enumerate(pr["kf2"]):
+            _fill_tri_keyframe(nb[j], kf, keep)
+        f12 = _arr(pr["f12"], np.float32).reshape(-1, 9) if k else np.zeros((1, 9), np.float32)
+        if len(f12) != max(k, 1):
+            raise ValueError("one F12 per neighbour")
+        p.k = k; p.kf2 = nb; p.f12 = f12.ctypes.data
+        p.only_stereo = 1 if pr.get("only_stereo") else 0
+        p.check_orientation = 1 if pr.get("check_orientation", self.mbCheckOrientation) else 0
+        p.triangulate = 1 if pr.get("triangulate", 1) else 0
+        p.chain = 1 if pr.get("chain", 1) else 0
+        p.ratio_factor = float(pr.get("ratio_factor", np.float32(1.5) * np.float32(1.2)))
+        o = dict(match=np.full((max(k, 1), max(n1, 1)), -1, np.int32), nmatches=np.zeros(max(k, 1), np.int32),
+                 x3d=np.zeros((max(k, 1), max(n1, 1), 3), np.float32), status=np.full((max(k, 1), max(n1, 1)), 255, np.uint8),
+                 nnew=np.full(1, -1, np.int32))
+        for name, v in o.items():
+            setattr(p, name, v.ctypes.data)
+        keep.append((nb, f12)); outs.append((o, k, n1, p.triangulate))
+    if all(f is None for f in frames):
+        rc = lib.ps_create_new_map_points(self._h, arr, n)
+    else:
+        handles = (ctypes.c_void_p * n)(*[None if f is None else f._h.value for f in frames])
+        rc = lib.ps_create_new_map_points_frames(self._h, arr, handles, n)
+    if not (partial_ok and rc == -3):
+        check(rc)
+    res = []
+    for o, k, n1, tri in outs:
+        r = dict(match=o["match"][:k, :n1].copy(), nmatches=o["nmatches"][:k].copy(), nnew=int(o["nnew"][0]), failed=int(o["nnew"][0]) < 0)
+        if tri:
+            r.update(status=o["status"][:k, :n1].copy(), x3d=o["x3d"][:k, :n1].copy())
+        res.append(r)
+    return res
+
+
+def _search_for_triangulation(self, kf1, kf2, F12, only_stereo):
+    """ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo): (nmatches, [(idx1, idx2), ...])."""
+    r = _create_new_map_points(self, [dict(kf1=kf1, kf2=[kf2], f12=np.asarray(F12, np.float32).reshape(1, 9), only_stereo=only_stereo,
+                                           triangulate=0, chain=0)])[0]
+    m = r["match"][0]
+    return int(r["nmatches"][0]), [(int(i), int(m[i])) for i in np.nonzero(m >= 0)[0]]
+
+
+ORBmatcher.CreateNewMapPoints = _create_new_map_points
+ORBmatcher.SearchForTriangulation = _search_for_triangulation

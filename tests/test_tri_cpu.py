@@ -1,0 +1,173 @@
+"""CPU checks around ps_create_new_map_points: the numpy second opinion (tests/tri_second_opinion.py) on a hand-built case whose
+answers are known by construction, the input condition of every seeded case the GPU file uses, and the presence of the C-ABI."""
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import tri_cases
+import tri_second_opinion as so
+
+F32 = np.float32
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FX, FY, CX, CY, BF = 700.0, 700.0, 600.0, 180.0, 350.0
+SIG = np.array([1.2 ** l for l in range(8)], F32)
+
+
+class _HandKeyframe:
+    """a camera at `centre` looking along +z (no rotation); features are appended one by one"""
+
+    def __init__(self, centre):
+        self.c = np.array(centre, np.float64)
+        self.rows = []
+
+    def project(self, X):
+        p = np.asarray(X, np.float64) - self.c
+        return FX * p[0] / p[2] + CX, FY * p[1] / p[2] + CY, p[2]
+
+    def add(self, u, v, desc, ur=-1.0, depth=-1.0, octave=0, occupied=0, node=7):
+        self.rows.append((u, v, ur, depth, octave, occupied, node, desc))
+        return len(self.rows) - 1
+
+    def see(self, X, desc, stereo=False, ur_error=0.0, **kw):
+        u, v, z = self.project(X)
+        return self.add(u, v, desc, u - BF / z + ur_error if stereo else -1.0, z if stereo else -1.0, **kw)
+
+    def dict(self):
+        r = self.rows
+        col = lambda i, dt: np.array([x[i] for x in r], dt)
+        ow = self.c.astype(F32)
+        return {"x": col(0, F32), "y": col(1, F32), "u_right": col(2, F32), "depth": col(3, F32), "octave": col(4, np.int32),
+                "occupied": col(5, np.uint8), "node": col(6, np.int32), "desc": np.array([x[7] for x in r], np.uint8).reshape(-1, 32),
+                "angle": np.zeros(len(r), F32), "R": np.eye(3, dtype=F32), "t": (-ow).astype(F32), "ow": ow,
+                "K8": (F32(FX), F32(FY), F32(CX), F32(CY), F32(1.0) / F32(FX), F32(1.0) / F32(FY), F32(BF) / F32(FX), F32(BF)),
+                "scale_factors": SIG, "level_sigma2": (SIG * SIG).astype(F32)}
+
+
+def _hand_case():
+    """Keyframe 1 at the origin; neighbour A behind and to the right (0.3, 0, -3), neighbour B ahead (0.3, 0, 3), neighbour C
+    0.1 m away (below the baseline mb = 0.5).  Three world points carry the created exits - Pa seen without depth by both
+    (linear triangulation), Pc near the axis with depth in keyframe 1 (UnprojectStereo(idx1)), Pd the same with depth in the
+    neighbour only (UnprojectStereo(idx2)) - and every other reachable exit gets one feature pair of its own.  Exit 4 (w == 0)
+    needs exactly parallel rays, which the parallax test sends elsewhere, and exit 9 (zero distance) needs x3D on a camera
+    centre, where z <= 0 comes first: neither can be reached from finite inputs, so neither has a pair here."""
+    rng = np.random.RandomState(5)
+    newd = lambda: rng.randint(0, 256, 32).astype(np.uint8)
+    k1, A, B, C = _HandKeyframe((0, 0, 0)), _HandKeyframe((0.3, 0, -3.0)), _HandKeyframe((0.3, 0, 3.0)), _HandKeyframe((0.1, 0, 0))
+    want = {}          # idx1 -> (neighbour, idx2, status, point or None)
+    Pa, Pc, Pd = (0.5, 0.2, 8.0), (0.05, 0.02, 10.0), (-0.04, 0.03, 12.0)
+    d = newd(); want[k1.see(Pa, d)] = (0, A.see(Pa, d), so.CREATED, Pa)
+    d = newd(); want[k1.see(Pc, d, stereo=True)] = (0, A.see(Pc, d), so.CREATED, Pc)
+    d = newd(); want[k1.see(Pd, d)] = (0, A.see(Pd, d, stereo=True), so.CREATED, Pd)
+    d = newd(); want[k1.see((0.3, -0.1, 9.0), d)] = (0, -1, so.NO_MATCH, None); A.see((0.3, -0.1, 9.0), newd())      # no descriptor within TH_LOW
+    d = newd(); want[k1.see((1.0, 0.3, 7.0), d, occupied=1)] = (0, -1, so.OCCUPIED, None); A.see((1.0, 0.3, 7.0), d)
+    far = (0.0, 0.5, 400.0)                                                                                      # rays almost parallel, no depth
+    d = newd(); want[k1.see(far, d)] = (0, A.see(far, d), so.LOW_PARALLAX, None)
+    behind1 = (-0.09, -0.03, -1.5)                                                                               # on keyframe 1's ray, behind it
+    d = newd(); u, v, _ = k1.project((0.09, 0.03, 1.5)); i1 = k1.add(u, v, d); want[i1] = (0, A.see(behind1, d), so.Z1, None)
+    d = newd(); want[k1.see((0.6, 0.1, 9.0), d, stereo=True, ur_error=6.0)] = (0, A.see((0.6, 0.1, 9.0), d), so.REPROJ1, None)
+    d = newd(); want[k1.see((-0.6, 0.1, 30.0), d)] = (0, A.see((-0.6, 0.1, 30.0), d, stereo=True, ur_error=6.0), so.REPROJ2, None)
+    d = newd(); want[k1.see((0.2, -0.3, 8.5), d, octave=0)] = (0, A.see((0.2, -0.3, 8.5), d, octave=7), so.SCALE_RATIO, None)
+    behind2 = (0.3 + 0.1, 0.05, 3.0 - 1.5)                                                                       # on neighbour B's ray, behind it
+    d = newd(); u, v, _ = B.project((0.3 - 0.1, -0.05, 3.0 + 1.5)); i2 = B.add(u, v, d); want[k1.see(behind2, d)] = (1, i2, so.Z2, None)
+    C.see(Pa, k1.rows[0][7])
+    kfs = [k.dict() for k in (k1, A, B, C)]
+    from pointslot_amd import keyframes
+    pr = keyframes.problem_of(kfs, check_orientation=0)
+    return pr, want
+
+
+def test_second_opinion_on_the_hand_built_case():
+    pr, want = _hand_case()
+    r = so.create_new_map_points(pr)
+    n1 = len(pr["kf1"]["node"])
+    assert r["nnew"] == 3
+    assert (r["status"][2] == so.SKIPPED).all() and r["nmatches"][2] == 0 and (r["match"][2] == -1).all()
+    for idx1, (nb, idx2, status, point) in want.items():
+        assert r["match"][nb, idx1] == idx2, (idx1, r["match"][:, idx1])
+        assert r["status"][nb, idx1] == status, (idx1, r["status"][:, idx1])
+        if point is not None:
+            assert np.allclose(r["x3d"][nb, idx1], point, rtol=2e-3, atol=2e-3), (idx1, r["x3d"][nb, idx1], point)
+        for other in (0, 1):        # in the other neighbour nothing resembles it - or its slot has been filled by then
+            if other != nb:
+                assert r["match"][other, idx1] == -1
+                assert r["status"][other, idx1] == (so.OCCUPIED if status in (so.CREATED, so.OCCUPIED) and (other > nb or status == so.OCCUPIED) else so.NO_MATCH)
+    kinds = {p["idx1"]: p["kind"] for p in r["pairs"]}
+    assert [kinds[i] for i in (0, 1, 2)] == ["svd", "stereo1", "stereo2"]
+    assert sorted(set(r["status"].ravel().tolist())) == [0, 1, 2, 3, 5, 6, 7, 8, 10, 11]
+    assert all(p["stable"] for p in r["pairs"]) and n1 == 11
+
+
+def test_second_opinion_winner_is_the_last_least_distance():
+    """two candidates at the same distance: the reference's `dist > bestDist` keeps the later one"""
+    pr, want = _hand_case()
+    kf2 = pr["kf2"][0]
+    for key in ("x", "y", "u_right", "depth", "octave", "desc", "node"):
+        kf2[key] = np.concatenate([kf2[key], kf2[key][:1]])
+    kf2["occupied"] = np.concatenate([kf2["occupied"], [0]]).astype(np.uint8)
+    kf2["angle"] = np.concatenate([kf2["angle"], [0]]).astype(F32)
+    nm, m = so.search_for_triangulation(pr["kf1"], kf2, pr["f12"][0], False, False)
+    assert m[0] == len(kf2["node"]) - 1
+
+
+@pytest.mark.parametrize("name", sorted(tri_cases.BUILDERS))
+def test_seeded_cases_are_well_posed(name):
+    """The input condition of tests/test_tri_gpu.py, checked here on the CPU: every triangulated pair of every seeded case is
+    stable (its verdict survives +-1 float32 ulp on x3D and on the stereo cosine) and has sigma1 / sigma3 <= 1e5, so that two
+    FP64 computations of the null vector agree far inside a float32 ulp.  No pair is left out of the GPU comparison."""
+    ref = tri_cases.reference(name)
+    bad = [p for p in ref["pairs"] if not p["stable"] or (p["kind"] == "svd" and not p["ratio"] <= 1e5)]
+    assert not bad, bad[:5]
+
+
+def test_seeded_cases_cover_what_they_are_named_for():
+    pr, ref = tri_cases.problem("tie"), tri_cases.reference("tie")
+    assert len(pr["expect_tie"]) >= 4
+    for (i, idx1), (low, high) in pr["expect_tie"].items():
+        assert high > low and ref["match"][i, idx1] == high
+    pr, ref = tri_cases.problem("shared_partner"), tri_cases.reference("shared_partner")
+    assert len(pr["expect_shared"]) >= 3
+    for s, d in pr["expect_shared"]:
+        assert ref["match"][0, s] == ref["match"][0, d] >= 0
+    for idx1, idx2 in tri_cases.problem("epipole_mono")["expect_epipole"]:
+        assert tri_cases.reference("epipole_mono")["match"][0, idx1] == -1
+    for idx1, idx2 in tri_cases.problem("epipole_stereo1")["expect_epipole"]:
+        assert tri_cases.reference("epipole_stereo1")["match"][0, idx1] == idx2
+    pr = tri_cases.problem("long_node")
+    assert max(np.bincount(kf["node"][kf["node"] >= 0] % 1000).max() for kf in pr["kf2"]) > 64
+    assert all((kf["node"] < 0).any() for kf in [tri_cases.problem("main")["kf1"]] + tri_cases.problem("main")["kf2"])
+    on, off = tri_cases.reference("chain_on"), tri_cases.reference("chain_off")
+    again = [(i, j) for i in (1, 2) for j in range(on["match"].shape[1]) if off["match"][i, j] >= 0 and (on["status"][:i, j] == 0).any()]
+    assert len(again) >= 5 and all(on["status"][i, j] == so.OCCUPIED and on["match"][i, j] == -1 for i, j in again)
+    assert on["nmatches"][1] < off["nmatches"][1]
+    ref = tri_cases.reference("baseline")
+    assert (ref["status"][1] == so.SKIPPED).all() and (ref["status"][0] != so.SKIPPED).all() and (ref["status"][2] != so.SKIPPED).all()
+    seen = set()
+    for name in tri_cases.BUILDERS:
+        if "status" in tri_cases.reference(name):
+            seen |= set(tri_cases.reference(name)["status"].ravel().tolist())
+    assert {0, 1, 2, 3, 5, 7, 8, 10, 11} <= seen
+    assert {p["kind"] for p in tri_cases.reference("main")["pairs"]} == {"svd", "stereo1", "stereo2", "none"}
+
+
+def test_abi_has_create_new_map_points(tmp_path):
+    """ps_create_new_map_points and ps_create_new_map_points_frames resolve in libpointslot_hip.so, and the structs of the header
+    have the documented sizes (also what pointslot_amd.matcher mirrors)."""
+    lib = os.path.join(ROOT, "pointslot_amd", "libpointslot_hip.so")
+    syms = subprocess.run(["nm", "-D", "--defined-only", lib], capture_output=True, text=True, check=True).stdout
+    for name in ("ps_create_new_map_points", "ps_create_new_map_points_frames"):
+        assert any(line.split()[-1] == name for line in syms.splitlines() if line.strip()), name
+    header = open(os.path.join(ROOT, "include", "pointslot_hip.h")).read()
+    assert "typedef struct ps_tri_keyframe" in header and "typedef struct ps_tri_problem" in header
+    # 12 pointers + n (padded) + 39 floats; kf1 + k + 2 pointers + 4 flags + ratio_factor + 5 pointers (LP64)
+    from pointslot_amd import matcher
+    assert ctypes.sizeof(matcher._TriKeyframe) == 256 and ctypes.sizeof(matcher._TriProblem) == 344
+    exe = str(tmp_path / "tri_abi_sizes")
+    src = exe + ".c"
+    with open(src, "w") as f:
+        f.write('#include "pointslot_hip.h"\n#include <stdio.h>\n#include <stddef.h>\nint main(void) { printf("%zu %zu %zu %zu\\n", sizeof(ps_tri_keyframe), '
+                'sizeof(ps_tri_problem), offsetof(ps_tri_problem, k), offsetof(ps_tri_problem, match)); return 0; }\n')
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), src, "-o", exe])
+    assert subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split() == ["256", "344", "256", "304"]

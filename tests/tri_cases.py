@@ -1,0 +1,130 @@
+"""The seeded CreateNewMapPoints cases of tests/test_tri_gpu.py, built once and shared with tests/test_tri_cpu.py, which checks
+on the CPU that every one of them is well-posed (all triangulated pairs stable, sigma1 / sigma3 <= 1e5 - see
+tests/tri_second_opinion.py).  Shapes: n1 = n2 = 300, 12 nodes, k = 3 unless a case says otherwise.  Test infrastructure."""
+import copy
+import functools
+
+import numpy as np
+
+from pointslot_amd import keyframes
+import tri_second_opinion as so
+
+F32 = np.float32
+_FEATURE_KEYS = ("x", "y", "octave", "angle", "u_right", "depth", "desc", "node")
+
+
+def _copy_feature(kf, src, dst, src_kf=None):
+    """feature dst of kf becomes a copy of feature src (of src_kf, default kf), unoccupied"""
+    s = kf if src_kf is None else src_kf
+    for key in _FEATURE_KEYS:
+        kf[key][dst] = s[key][src]
+    kf["occupied"][dst] = 0
+
+
+def _matched(pr):
+    return so.create_new_map_points(pr)
+
+
+def _tie():
+    """duplicated descriptors inside one node: the matched feature of the neighbour is repeated at a higher index"""
+    pr = keyframes.tri_problem(21)
+    ref = _matched(pr)
+    moved = {}
+    for i in range(len(pr["kf2"])):
+        kf2 = pr["kf2"][i]
+        taken = set(int(v) for v in ref["match"][i] if v >= 0)
+        done = 0
+        for idx1 in np.nonzero(ref["match"][i] >= 0)[0]:
+            idx2 = int(ref["match"][i, idx1])
+            free = [j for j in range(idx2 + 1, len(kf2["node"])) if j not in taken]
+            if not free or done == 4:
+                continue
+            _copy_feature(kf2, idx2, free[-1])
+            taken.add(free[-1]); moved[(i, int(idx1))] = (idx2, free[-1]); done += 1
+    pr["expect_tie"] = moved
+    return pr
+
+
+def _shared_partner():
+    """two features of keyframe 1 choose the same feature of the neighbour"""
+    pr = keyframes.tri_problem(22)
+    ref = _matched(pr)
+    kf1 = pr["kf1"]
+    src = [int(i) for i in np.nonzero(ref["match"][0] >= 0)[0]][:5]
+    free = [int(i) for i in np.nonzero((ref["match"] < 0).all(axis=0))[0] if i not in src][:5]
+    for s, d in zip(src, free):
+        _copy_feature(kf1, s, d)
+    pr["expect_shared"] = list(zip(src, free))
+    return pr
+
+
+def _epipole(stereo1):
+    """a mono feature of the neighbour moved onto the epipole: on every epipolar line, and inside the disc of ORBmatcher.cc:870-876"""
+    pr = keyframes.tri_problem(23)
+    ref = _matched(pr)
+    kf1, kf2 = pr["kf1"], pr["kf2"][0]
+    R2, t2, Cw = kf2["R"].astype(np.float64), kf2["t"].astype(np.float64), kf1["ow"].astype(np.float64)
+    C2 = R2 @ Cw + t2
+    ex, ey = F32(kf2["K8"][0] * C2[0] / C2[2] + kf2["K8"][2]), F32(kf2["K8"][1] * C2[1] / C2[2] + kf2["K8"][3])
+    chosen = []
+    for idx1 in np.nonzero(ref["match"][0] >= 0)[0][:6]:
+        idx2 = int(ref["match"][0, idx1])
+        kf2["x"][idx2], kf2["y"][idx2], kf2["u_right"][idx2], kf2["depth"][idx2] = ex, ey, -1.0, -1.0
+        if stereo1:
+            kf1["u_right"][idx1], kf1["depth"][idx1] = kf1["x"][idx1] - F32(12.0), F32(32.0)
+        else:
+            kf1["u_right"][idx1], kf1["depth"][idx1] = -1.0, -1.0
+        chosen.append((int(idx1), idx2))
+    pr["expect_epipole"] = chosen
+    return pr
+
+
+def _sizes(seed, n1, n2s, **kw):
+    kfs = keyframes.keyframe_set(seed, n_kf=1 + len(n2s), sizes=[n1] + list(n2s), **kw)
+    return keyframes.problem_of(kfs)
+
+
+BUILDERS = {
+    "main": lambda: keyframes.tri_problem(11),
+    "noisy": lambda: keyframes.tri_problem(12, noise=2.0, flip_bits=16),
+    "raw": lambda: keyframes.tri_problem(13, raw_shift=0.75),
+    "no_orientation": lambda: keyframes.tri_problem(14, check_orientation=0),
+    "search_00": lambda: keyframes.tri_problem(15, only_stereo=0, check_orientation=0, triangulate=0, chain=0),
+    "search_01": lambda: keyframes.tri_problem(15, only_stereo=0, check_orientation=1, triangulate=0, chain=0),
+    "search_10": lambda: keyframes.tri_problem(15, only_stereo=1, check_orientation=0, triangulate=0, chain=0),
+    "search_11": lambda: keyframes.tri_problem(15, only_stereo=1, check_orientation=1, triangulate=0, chain=0),
+    "only_stereo_tri": lambda: keyframes.tri_problem(16, only_stereo=1),
+    "tie": _tie,
+    "shared_partner": _shared_partner,
+    "long_node": lambda: keyframes.tri_problem(24, n_nodes=2),
+    "epipole_mono": lambda: _epipole(False),
+    "epipole_stereo1": lambda: _epipole(True),
+    "chain_on": lambda: keyframes.tri_problem(25, p_occupied=0.05, chain=1),
+    "chain_off": lambda: keyframes.tri_problem(25, p_occupied=0.05, chain=0),
+    "baseline": lambda: keyframes.tri_problem(26, step=[0.0, 1.0, 0.3, 2.0]),
+    "empty_kf1": lambda: _sizes(27, 0, [300, 300]),
+    "empty_neighbour": lambda: _sizes(28, 300, [300, 0, 300]),
+    "no_neighbours": lambda: _sizes(29, 300, []),
+    "k32": lambda: keyframes.tri_problem(30, k=32, n1=60, n2=60, n_nodes=4, step=0.7),
+    "batch_0": lambda: _sizes(31, 300, [300, 300, 300]),
+    "batch_1": lambda: _sizes(32, 70, [130]),
+    "batch_2": lambda: _sizes(33, 257, [64, 65, 1, 300, 129]),
+    "batch_3": lambda: _sizes(34, 1, [300, 300]),
+    "batch_4": lambda: _sizes(35, 199, [211, 0, 97, 5]),
+}
+BATCH = ("batch_0", "batch_1", "batch_2", "batch_3", "batch_4")
+
+
+@functools.lru_cache(maxsize=None)
+def _built(name):
+    pr = BUILDERS[name]()
+    return pr, so.create_new_map_points(pr)
+
+
+def problem(name):
+    """a private copy of the case's problem dict (the arrays are shared: do not write into them)"""
+    return copy.copy(_built(name)[0])
+
+
+def reference(name):
+    return _built(name)[1]
