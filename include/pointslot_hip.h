@@ -466,6 +466,99 @@ int ps_create_new_map_points(ps_matcher* m, ps_tri_problem* probs, int nprob);
  * read k times. */
 int ps_create_new_map_points_frames(ps_matcher* m, ps_tri_problem* probs, ps_frame* const* kf1_frames, int nprob);
 
+/* ------------------------------------------------------------------------------------------------
+ * Bag of words - the DBoW2 vocabulary the reference keeps as ORBVocabulary (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h with
+ * FORB), Frame::ComputeBoW / KeyFrame::ComputeBoW (src/Frame.cc:2040-2047, src/KeyFrame.cc:114-123) and the two
+ * ORBmatcher::SearchByBoW overloads (src/ORBmatcher.cc:280-410, :646-781).
+ *
+ * ps_vocabulary is an opaque, immutable tree in HBM, built once per device and read by any number of matcher handles on any
+ * number of threads.  It has no stream of its own: the work of a call runs on the ps_matcher passed to it.  A vocabulary and a
+ * matcher on different devices make the call return PS_ERR_INVALID.
+ *
+ * ps_vocabulary_create takes the records of the binary file in file order (loadFromBinaryFile, TemplatedVocabulary.h:1343-1384):
+ * record i becomes node i + 1, the root is node 0; parent[i] is the record's parent id, desc[i] its 32-byte descriptor,
+ * weight[i] its weight, is_leaf[i] != 0 makes it a word.  Children are listed in record order (children.push_back, :1368) and
+ * word ids are assigned in order of the leaf records (:1372-1377).  Accepted: 1 <= k <= 20, 1 <= L <= 10, weighting 0 TF_IDF,
+ * 1 TF, 2 IDF, 3 BINARY (BowVector.h), scoring 0 (L1_NORM) only.  k and L are recorded as the file states them; a node may have
+ * any number of children and a leaf may sit at any depth, as in the reference.  Rejected with PS_ERR_INVALID - where the
+ * reference runs into undefined behaviour: a parent id that does not precede its child (parent[i] < 0 or > i), a parent that is
+ * a leaf, an inner node (the root included) with no children.
+ *
+ * ps_vocabulary_load_binary reads the layout the reference reads: u32 nb_nodes, u32 size_node (= 41), then k, L, scoring,
+ * weighting as i32; nb_nodes records of i32 parent, 32 B descriptor, f32 weight, u8 leaf.  Exactly nb_nodes records are read
+ * and the file must end there.  The reference's `while(!f.eof())` (:1361) makes one more pass over the stale buffer after the
+ * last record and writes m_nodes[nb_nodes + 1], one past the vector: undefined behaviour, which is not modelled.  The parser is
+ * host-only (csrc/vocab_file.h).  PS_ERR_INVALID: unreadable, truncated or inconsistent file. */
+typedef struct ps_vocabulary ps_vocabulary;
+int ps_vocabulary_create(int device, int k, int L, int scoring, int weighting, int nnodes, const int32_t* parent, const uint8_t* desc,
+                         const float* weight, const uint8_t* is_leaf, ps_vocabulary** out);
+int ps_vocabulary_load_binary(int device, const char* path, ps_vocabulary** out);
+void ps_vocabulary_destroy(ps_vocabulary* v);
+/* k, L as given; nodes = nnodes + 1 (the root included); words = leaf records.  Any pointer may be NULL. */
+int ps_vocabulary_info(const ps_vocabulary* v, int32_t* k, int32_t* L, int32_t* nodes, int32_t* words);
+
+/* TemplatedVocabulary::transform(features, BowVector&, FeatureVector&, levelsup) (TemplatedVocabulary.h:1133-1200 over the
+ * per-feature descent :1224-1265) for a batch of frames.  Per problem, in: n descriptors and levelsup; out:
+ *   word[n]   : the WordId of feature i, -1 for a stopped word
+ *   node[n]   : the NodeId met at level L - levelsup on the way down, the root 0 when that level is <= 0 (:1233), -1 for a stopped
+ *               word - exactly what ps_tri_keyframe.node and ps_bow_side.node take; the FeatureVector is node -> features in
+ *               ascending feature order (addFeature's order)
+ *   bow_id[], bow_val[], bow_n : the BowVector, ids ascending as std::map iterates, values double; room for n entries each
+ * The descent takes the first child of least Hamming distance (`d < best_d` is strict, :1250: on ties the earliest child wins)
+ * until it stands on a leaf.  A word of weight <= 0 is stopped (:1163, :1191): it appears in neither vector.  TF_IDF and TF sum
+ * the weights per word (addWeight), IDF and BINARY keep the first (addIfNotExist); the L1 normalisation of BowVector.cpp:62-84
+ * follows (the sum of |values| is formed in an order of the kernel's own; skipped when it is not > 0).
+ * Modelling choice: a leaf shallower than level L - levelsup leaves *nid unwritten in the reference (:1257 never fires), so
+ * its callers read an uninitialised local; here node is then that leaf's own id.
+ * Limits: n <= 8191 per problem; a problem beyond that fails alone (bow_n = -1, outputs untouched) and the call returns
+ * PS_ERR_CAPACITY after serving the others.  n == 0 is valid. */
+typedef struct ps_bow_problem {
+  int32_t n;
+  const uint8_t* desc;   /* [n][32] */
+  int32_t levelsup;
+  int32_t* word;         /* out [n] */
+  int32_t* node;         /* out [n] */
+  int32_t* bow_id;       /* out [<= n] */
+  double* bow_val;       /* out [<= n] */
+  int32_t bow_n;         /* out */
+} ps_bow_problem;
+int ps_bow_transform(ps_matcher* m, const ps_vocabulary* v, ps_bow_problem* probs, int nprob);
+
+/* ORBmatcher::SearchByBoW, both overloads, batched.  Side a is pKF / pKF1, side b is F / pKF2:
+ *   n, desc = mDescriptors rows; angle: see the modes; node[i] = the id of the mFeatVec node that lists feature i (-1: none -
+ *   ps_bow_transform's node[]); has_point[i] = pMP && !pMP->isBad() for the side's GetMapPointMatches()[i].
+ * Common rules.  The features of a node are taken in ascending index on both sides (mFeatVec's order); only nodes present on
+ * both sides are searched (:302-386, :676-758); a feature of side a without a point is skipped.  `dist<bestDist1` (:338, :712)
+ * makes the first admitted candidate of least distance the best; bestDist2 ends as the least distance over all other admitted
+ * candidates (256 if none), so an equal distance makes the ratio test fail for nn_ratio <= 1.  The ratio test
+ * (float)bestDist1 < nn_ratio * (float)bestDist2 is in float as written.  check_orientation applies the 30-bin histogram
+ * (round(rot * 30 / 360), bin 30 -> 0) and ComputeThreeMaxima to the accepted matches.
+ *   mode 0 (KeyFrame*, Frame&, :280-410): a candidate of b is admitted unless an earlier feature of a has taken it
+ *     (vpMapPointMatches[realIdxF], :331 - a feature sits in one node only, so only the order within the node matters); accepted
+ *     when bestDist1 <= 50; match is [b.n] and holds the index into a (the MapPoint of pKF the reference stores), -1 = NULL;
+ *     b.has_point is ignored (may be NULL); a.angle = pKF->mvKeysUn, b.angle = F.mvKeys (:356-360).
+ *   mode 1 (KeyFrame*, KeyFrame*, :646-781): a candidate needs b.has_point and must not be in vbMatched2 (:702); accepted when
+ *     bestDist1 < 50 - strict, unlike mode 0; match is [a.n] and holds the index into b; both angles are mvKeysUn.
+ * nmatches is the return value.  Limits: n <= 8191 per side; a problem beyond that fails alone (nmatches = -1, match untouched)
+ * and the call returns PS_ERR_CAPACITY after serving the others.  Empty sides and disjoint node sets are valid and give
+ * empty results. */
+typedef struct ps_bow_side {
+  int32_t n;
+  const uint8_t* desc;       /* [n][32] */
+  const float* angle;
+  const int32_t* node;
+  const uint8_t* has_point;
+} ps_bow_side;
+typedef struct ps_bow_search_problem {
+  ps_bow_side a, b;
+  int32_t mode;
+  float nn_ratio;
+  int32_t check_orientation;
+  int32_t* match;            /* out: mode 0 [b.n], mode 1 [a.n] */
+  int32_t nmatches;          /* out */
+} ps_bow_search_problem;
+int ps_search_by_bow(ps_matcher* m, ps_bow_search_problem* probs, int nprob);
+
 
 /* ------------------------------------------------------------------------------------------------
  * Optimiser — replaces the hot static members of ORB_SLAM2::Optimizer

@@ -10,6 +10,7 @@
 #include <vector>
 #include "frame_host.h"
 #include "match_plan.h"
+#include "matcher_host.h"
 #include "tri_plan.h"
 #include "ps_common.h"
 
@@ -23,20 +24,6 @@ void psk_distinctive_launch(const uint8_t*, const int32_t*, int32_t*, int, hipSt
 void psk_frame_stage_launch(const FrameStageJob*, int, const FrameStageDst*, hipStream_t);
 void psk_tri_launch(const TriArrays*, int, int, int, hipStream_t);
 }
-
-struct ps_matcher {
-  std::mutex mu;              // calls on one handle are serialised (a handle may be shared by threads)
-  int device = 0;
-  hipStream_t stream = nullptr;
-  uint8_t* d_buf = nullptr;   // one growable device arena
-  size_t d_bytes = 0;
-  uint8_t* h_buf = nullptr;   // pinned staging of the same size
-  size_t h_bytes = 0;
-  uint8_t* d_wide = nullptr;  // second arena, only for the wide re-run of search problems whose windows overflowed the candidate store
-  size_t d_wide_bytes = 0;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;   // around the kernels of the last brute-force / projection / triangulation call (ps_matcher_last_kernel_ms)
-  float last_kernel_ms = 0;
-};
 
 namespace {
 inline size_t al(size_t v) { return (v + 255) / 256 * 256; }
@@ -114,6 +101,8 @@ int frame_use_stage(FrameUse& U, ps_matcher* m, const FrameStageJob* d_jobs, con
   return rc;
 }
 }  // namespace
+
+int psm_ensure(ps_matcher* m, size_t need) { return ensure(m, need); }
 
 extern "C" {
 

@@ -102,6 +102,15 @@ class ORBmatcher {
     for (int i = 0; i < n; i++) total += *p[i].nnew;
     return total;
   }
+  // both SearchByBoW overloads on caller-filled problems (include/pointslot_hip.h: ps_bow_search_problem; mode, nn_ratio and
+  // check_orientation are the caller's, so one call may mix overloads and settings).  Returns the summed match count.
+  int SearchByBoWBatch(ps_bow_search_problem* p, int n) {
+    if (n <= 0) return 0;
+    if (ps_search_by_bow(h_, p, n) != PS_OK) throw std::runtime_error(ps_last_error());
+    int total = 0;
+    for (int i = 0; i < n; i++) total += p[i].nmatches;
+    return total;
+  }
   ps_matcher* handle() { return h_; }   // (kernel time of the last call: ps_matcher_last_kernel_ms)
   static float RadiusByViewingCos(const float& viewCos) { return viewCos > 0.998 ? 2.5f : 4.0f; }   // ORBmatcher.cc:252-258
 
@@ -242,7 +251,64 @@ class ORBmatcher {
     return nmatches;
   }
 
+  // int SearchByBoW(KeyFrame *pKF, Frame &F, std::vector<MapPoint*> &vpMapPointMatches)                                    :280-410
+  // over KeyFrame- and Frame-shaped types (KeyFrame.h: N, mvKeysUn, mDescriptors, mFeatVec, GetMapPointMatches; Frame.h: N, mvKeys,
+  // mDescriptors, mFeatVec; tests/cpp/bow_view.h).  mFeatVec is what ORBVocabulary::transform filled (ComputeBoW).
+  template <class KeyFrameT, class FrameT, class MapPointT, class = typename std::enable_if<!std::is_pointer<FrameT>::value>::type>
+  int SearchByBoW(KeyFrameT* pKF, FrameT& F, std::vector<MapPointT*>& vpMapPointMatches) {
+    const std::vector<MapPointT*> vpMapPointsKF = pKF->GetMapPointMatches();
+    vpMapPointMatches.assign((std::size_t)F.N, static_cast<MapPointT*>(NULL));
+    BowSide A, B;
+    ps_bow_search_problem p = ps_bow_search_problem{};
+    fillBowSide(A, p.a, pKF->N, pKF->mDescriptors, pKF->mvKeysUn, pKF->mFeatVec, &vpMapPointsKF);
+    fillBowSide(B, p.b, F.N, F.mDescriptors, F.mvKeys, F.mFeatVec, (const std::vector<MapPointT*>*)nullptr);
+    std::vector<int32_t> match((std::size_t)std::max(F.N, 1), -1);
+    p.mode = 0; p.nn_ratio = mfNNratio; p.check_orientation = mbCheckOrientation ? 1 : 0; p.match = match.data();
+    SearchByBoWBatch(&p, 1);
+    for (int j = 0; j < F.N; j++)
+      if (match[j] >= 0) vpMapPointMatches[j] = vpMapPointsKF[match[j]];
+    return p.nmatches;
+  }
+
+  // int SearchByBoW(KeyFrame *pKF1, KeyFrame *pKF2, std::vector<MapPoint*> &vpMatches12)                                   :646-781
+  template <class KeyFrameT, class MapPointT>
+  int SearchByBoW(KeyFrameT* pKF1, KeyFrameT* pKF2, std::vector<MapPointT*>& vpMatches12) {
+    const std::vector<MapPointT*> vpMapPoints1 = pKF1->GetMapPointMatches(), vpMapPoints2 = pKF2->GetMapPointMatches();
+    vpMatches12.assign(vpMapPoints1.size(), static_cast<MapPointT*>(NULL));
+    BowSide A, B;
+    ps_bow_search_problem p = ps_bow_search_problem{};
+    fillBowSide(A, p.a, pKF1->N, pKF1->mDescriptors, pKF1->mvKeysUn, pKF1->mFeatVec, &vpMapPoints1);
+    fillBowSide(B, p.b, pKF2->N, pKF2->mDescriptors, pKF2->mvKeysUn, pKF2->mFeatVec, &vpMapPoints2);
+    std::vector<int32_t> match((std::size_t)std::max(pKF1->N, 1), -1);
+    p.mode = 1; p.nn_ratio = mfNNratio; p.check_orientation = mbCheckOrientation ? 1 : 0; p.match = match.data();
+    SearchByBoWBatch(&p, 1);
+    for (int i = 0; i < pKF1->N && i < (int)vpMatches12.size(); i++)
+      if (match[i] >= 0) vpMatches12[i] = vpMapPoints2[match[i]];
+    return p.nmatches;
+  }
+
  protected:
+  // one side of SearchByBoW as ps_bow_side's arrays; points == nullptr: the Frame side of the first overload
+  struct BowSide {
+    std::vector<float> angle;
+    std::vector<int32_t> node;
+    std::vector<uint8_t> desc, has_point;
+  };
+  template <class KeysT, class FeatVecT, class MapPointT>
+  static void fillBowSide(BowSide& S, ps_bow_side& s, int n, const pscv::Mat& descriptors, const KeysT& keys, const FeatVecT& featVec,
+                          const std::vector<MapPointT*>* points) {
+    const int m = std::max(n, 1);
+    S.angle.assign(m, 0.f); S.node.assign(m, -1); S.has_point.assign(m, 0);
+    for (int i = 0; i < n; i++) {
+      S.angle[i] = keys[i].angle;
+      if (points && (std::size_t)i < points->size()) S.has_point[i] = ((*points)[i] && !(*points)[i]->isBad()) ? 1 : 0;
+    }
+    for (const auto& nodeAndFeatures : featVec)
+      for (const auto i : nodeAndFeatures.second)
+        if ((std::size_t)i < (std::size_t)n) S.node[i] = (int32_t)nodeAndFeatures.first;
+    S.desc = rows32(descriptors, n);
+    s.n = n; s.desc = S.desc.data(); s.angle = S.angle.data(); s.node = S.node.data(); s.has_point = points ? S.has_point.data() : nullptr;
+  }
   // one KeyFrame as ps_tri_keyframe's arrays
   struct TriSide {
     std::vector<float> x, y, xr, yr, angle, ur, depth;

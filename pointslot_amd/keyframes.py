@@ -27,11 +27,15 @@ def compute_f12(kf1, kf2):
 
 
 def keyframe_set(seed, n_kf=4, n=300, n_nodes=12, step=1.0, noise=0.5, flip_bits=10, p_wrong=0.1, p_none=0.05, p_occupied=0.25,
-                 p_seen=0.85, stereo_depth=25.0, p_stereo=0.85, raw_shift=0.0, w=1241, h=376, sizes=None):
+                 p_seen=0.85, stereo_depth=25.0, p_stereo=0.85, raw_shift=0.0, w=1241, h=376, sizes=None, descriptor_families=None):
     """n_kf keyframes; [0] is the current one, [i] lies about i * step metres behind it (step: a sequence gives one distance per
     keyframe instead).  Every keyframe has n features (sizes: one count per keyframe instead): projections of shared world
     points where enough are visible, random clutter otherwise, in an order of the keyframe's own.  raw_shift: mvKeys differ from
-    mvKeysUn by that many pixels (x_raw, y_raw); 0 leaves them out."""
+    mvKeysUn by that many pixels (x_raw, y_raw); 0 leaves them out.  descriptor_families = (families, members, spread): the first
+    families * members world points come in groups that share a vocabulary node and a base descriptor, each member up to `spread`
+    bits away from it - repetitive texture, where the nearest and the second nearest candidate are close (independent random
+    descriptors are about 128 bits apart, and no ratio test or already-matched rule ever decides anything).  Off by default; it
+    draws from a generator of its own, so the bytes of every other configuration stay as they are."""
     rng = synth.Rng(seed)
     fx, fy, cx, cy = KITTI_K
     sig, _ = synth._level_sigma()
@@ -47,6 +51,16 @@ def keyframe_set(seed, n_kf=4, n=300, n_nodes=12, step=1.0, noise=0.5, flip_bits
     base_ang = rng.uniform(npts, 0, 360)
     node_ids = (1000 + 37 * np.arange(max(n_nodes, 1))).astype(np.int32)
     base_node = rng.integers(npts, 0, max(n_nodes, 1))
+    if descriptor_families:
+        fam, members, spread = [int(v) for v in descriptor_families]
+        frng = synth.Rng(int(seed) * 7919 + 104729)
+        fam = min(fam, npts // max(members, 1))
+        fam_desc = frng.integers(fam * 32, 0, 256).astype(np.uint8).reshape(fam, 32)
+        fam_node = frng.integers(fam, 0, max(n_nodes, 1))
+        for f in range(fam):
+            for j in range(members):
+                base_desc[f * members + j] = synth._flip(frng, fam_desc[f], spread)
+                base_node[f * members + j] = fam_node[f]
     out = []
     for i in range(n_kf):
         ni = sizes[i]
@@ -103,3 +117,11 @@ def problem_of(kfs, only_stereo=0, check_orientation=1, triangulate=1, chain=1):
     f12 = np.stack([compute_f12(kfs[0], kf) for kf in kfs[1:]]) if len(kfs) > 1 else np.zeros((0, 3, 3), F32)
     return {"kf1": kfs[0], "kf2": kfs[1:], "f12": f12, "only_stereo": only_stereo, "check_orientation": check_orientation,
             "triangulate": triangulate, "chain": chain, "ratio_factor": F32(1.5) * F32(1.2)}
+
+
+def bow_pair(seed, na=300, nb=300, n_nodes=12, families=(40, 6, 8), flip_bits=8, p_point=0.8, **kw):
+    """Two views of one scene as the sides of ORBmatcher::SearchByBoW (ps_bow_side): the keyframe dicts of keyframe_set with
+    has_point (= occupied, drawn with p_point) added; "point" is the world point behind a feature, -1 for clutter.  Side a is
+    pKF / pKF1, side b is F / pKF2."""
+    kfs = keyframe_set(seed, n_kf=2, sizes=[na, nb], n_nodes=n_nodes, flip_bits=flip_bits, p_occupied=p_point, descriptor_families=families, **kw)
+    return tuple(dict(kf, has_point=kf["occupied"]) for kf in kfs)

@@ -427,3 +427,69 @@ def _search_for_triangulation(self, kf1, kf2, F12, only_stereo):
 
 ORBmatcher.CreateNewMapPoints = _create_new_map_points
 ORBmatcher.SearchForTriangulation = _search_for_triangulation
+
+
+# ---- ORBmatcher::SearchByBoW, both overloads (ps_search_by_bow) ------------------------------------------------------------
+class _BowSide(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_int32), ("desc", ctypes.c_void_p), ("angle", ctypes.c_void_p), ("node", ctypes.c_void_p),
+                ("has_point", ctypes.c_void_p)]
+
+
+class _BowSearchProblem(ctypes.Structure):
+    _fields_ = [("a", _BowSide), ("b", _BowSide), ("mode", ctypes.c_int32), ("nn_ratio", ctypes.c_float),
+                ("check_orientation", ctypes.c_int32), ("match", ctypes.c_void_p), ("nmatches", ctypes.c_int32)]
+
+
+lib.ps_search_by_bow.argtypes = [ctypes.c_void_p, ctypes.POINTER(_BowSearchProblem), ctypes.c_int]
+
+
+def _fill_bow_side(c, side, keep, need_points):
+    """one ps_bow_side from a dict: desc [n, 32], angle [n], node [n] (ps_bow_transform's node[]), has_point [n] (optional on the
+    Frame side of mode 0)"""
+    a = dict(desc=_arr(side["desc"], np.uint8).reshape(-1, 32), angle=_arr(side["angle"], np.float32), node=_arr(side["node"], np.int32))
+    if need_points or side.get("has_point") is not None:
+        a["has_point"] = _arr(side["has_point"], np.uint8)
+    n = len(a["node"])
+    if any(len(v) != n for v in a.values()):
+        raise ValueError("the arrays of a side differ in length")
+    keep.append(a)
+    c.n = n
+    for k, v in a.items():
+        setattr(c, k, v.ctypes.data)
+    return n
+
+
+def _search_by_bow(self, problems, partial_ok=False):
+    """ORBmatcher::SearchByBoW for a batch.  problems: list of dicts {a, b: sides as in _fill_bow_side, mode: 0 (KeyFrame*, Frame&)
+    or 1 (KeyFrame*, KeyFrame*), nn_ratio and check_orientation (default: the matcher's)}.  Returns per problem
+    (nmatches, match int32): mode 0 [b.n] holding indices into a, mode 1 [a.n] holding indices into b, -1 = NULL; nmatches = -1
+    for a problem beyond the limits when partial_ok lets the call return after PS_ERR_CAPACITY."""
+    n = len(problems)
+    if n == 0:
+        return []
+    arr = (_BowSearchProblem * n)()
+    keep, outs = [], []
+    for i, pr in enumerate(problems):
+        p = arr[i]
+        p.mode = int(pr.get("mode", 0))
+        na = _fill_bow_side(p.a, pr["a"], keep, True)
+        nb = _fill_bow_side(p.b, pr["b"], keep, p.mode == 1)
+        p.nn_ratio = float(pr.get("nn_ratio", self.mfNNratio))
+        p.check_orientation = 1 if pr.get("check_orientation", self.mbCheckOrientation) else 0
+        m = nb if p.mode == 0 else na
+        out = np.full(max(m, 1), -3, np.int32)
+        p.match = out.ctypes.data; p.nmatches = -2
+        outs.append((out, m))
+    rc = lib.ps_search_by_bow(self._h, arr, n)
+    if not (partial_ok and rc == -3):
+        check(rc)
+    return [(int(arr[i].nmatches), outs[i][0][:outs[i][1]].copy()) for i in range(n)]
+
+
+def _search_by_bow_one(self, a, b, mode=0):
+    """SearchByBoW(pKF, F, vpMapPointMatches) (mode 0) / SearchByBoW(pKF1, pKF2, vpMatches12) (mode 1) for one pair"""
+    return _search_by_bow(self, [dict(a=a, b=b, mode=mode)])[0]
+
+
+ORBmatcher.SearchByBoWBatch = _search_by_bow
+ORBmatcher.SearchByBoW = _search_by_bow_one
