@@ -559,6 +559,93 @@ typedef struct ps_bow_search_problem {
 } ps_bow_search_problem;
 int ps_search_by_bow(ps_matcher* m, ps_bow_search_problem* probs, int nprob);
 
+/* ------------------------------------------------------------------------------------------------
+ * Keyframe database - KeyFrameDatabase (src/KeyFrameDatabase.cc:41-310): add, erase, clear, DetectLoopCandidates and
+ * DetectRelocalizationCandidates, and the `mpORBVocabulary->score` of LoopClosing::DetectLoop's minScore loop
+ * (src/LoopClosing.cc:127-141, Thirdparty/DBoW2/DBoW2/ScoringObject.cpp:23-68).  It turns the BowVectors ps_bow_transform
+ * writes into the candidate keyframes ps_search_by_bow is then run over.
+ *
+ * ps_kfdb is an opaque, mutable store in HBM: one row of word ids and one row of values per keyframe (a forward store; the
+ * reference's inverted file is not kept).  Like ps_vocabulary it has no stream of its own: add, query and score run on the
+ * ps_matcher passed to them and return when the work is done.  A database and a matcher on different devices make the call
+ * return PS_ERR_INVALID.  Calls on one database are serialised.
+ *
+ * ps_kfdb_create: capacity = the number of live keyframes it can hold, 1 .. 4096; max_words = the longest BowVector it
+ * stores, 1 .. 8191.  It takes capacity * roundup(max_words, 64) * 12 bytes of device memory.
+ * ps_kfdb_add stores n keyframes under caller-chosen ids.  bow_id[e] / bow_val[e] / bow_n[e] are entry e's BowVector exactly
+ * as ps_bow_transform writes it: ids ascending, values double.  bow_n[e] == 0 is valid: such a keyframe can never be found.
+ * PS_ERR_INVALID, nothing stored: a null or negative argument, ids of a vector not strictly ascending or negative, an id that is
+ * already stored or appears twice in the call (the reference would list such a keyframe twice and count its words double: not
+ * modelled).  An entry with more than max_words words, and an entry for which no room is left, fails alone: the call returns
+ * PS_ERR_CAPACITY after storing the others.  stored (may be NULL) receives 1 per stored entry, 0 per failed one.  A database
+ * takes 2^32 - 1 adds between two ps_kfdb_clear; further ones fail with PS_ERR_CAPACITY.
+ * ps_kfdb_erase removes the named keyframes; unknown ids are ignored, as in the reference's loop (:59-66).  ps_kfdb_clear
+ * removes all.  ps_kfdb_size: the number of live keyframes.
+ *
+ * ps_kfdb_query serves a batch of queries up to the scored sharing list (:79-140, :202-254).  Per problem, in: the query's
+ * BowVector (n <= 8191, ids strictly ascending), mode 0 = DetectRelocalizationCandidates, 1 = DetectLoopCandidates, and for mode 1
+ * excluded[nexcluded] = the ids of pKF->GetConnectedKeyFrames() (ids that are not stored are ignored).  Out, with room for
+ * ps_kfdb_size entries each:
+ *   share_id[], nshare : lKFsSharingWords in the reference's order.  Its walk goes over the query's words in ascending id and,
+ *                  inside a word's list, in push_back order, and lists a keyframe where it meets it first: a keyframe's place is
+ *                  the pair (least word it has in common with the query, its add order).  erase keeps the order of the others; a
+ *                  keyframe erased and added again goes to the back.  In mode 1 an excluded keyframe is never listed and takes
+ *                  no part in maxCommonWords (:97-101).
+ *   share_words[]    : mnRelocWords / mnLoopWords, the number of common words
+ *   min_common_words : `int minCommonWords = maxCommonWords*0.8f` - the int-to-float product, truncated (0 for an empty list)
+ *   share_score[]    : a keyframe is scored when words > min_common_words: (float)score(query, keyframe), L1Scoring::score with
+ *                  the query as v1 - the double sum of fabs(vi - wi) - fabs(vi) - fabs(wi) over the common words in ascending
+ *                  word id, one addition after the other, then -score/2.0, rounded to float once.
+ *                  mode 1: that score where words > min_common_words, 0 elsewhere (mLoopScore is only read behind that test).
+ *                  mode 0: the keyframe's reloc_score after this query - fresh for the scored keyframes, stale for the others.
+ * Modelling choice (reloc_score).  KeyFrame's constructor does not initialise mRelocScore (KeyFrame.cc:43), and the covisibility
+ * stage of DetectRelocalizationCandidates adds it for every neighbour that shares a word (:274-277), scored by this query or
+ * not: it reads what the last earlier relocalisation query wrote, or indeterminate memory.  The database keeps one reloc_score
+ * float per stored keyframe: 0.0f at add, written whenever a mode-0 query scores the keyframe, kept from query to query and
+ * from call to call.  The queries of one call are served in array order with respect to it: the results do not depend on how
+ * the queries are split over calls.
+ * A problem with n > 8191 fails alone (nshare = -1, outputs untouched) and the call returns PS_ERR_CAPACITY after serving the
+ * others.  An empty query and an empty database give nshare = 0.  At most 65535 problems per call.
+ *
+ * ps_kfdb_score: out[i] = L1Scoring::score(query, stored keyframe ids[i]) in double, the same ordered sum.  An unknown id gives
+ * NaN in its place and the call returns PS_ERR_INVALID after writing the others.
+ *
+ * ps_kfdb_select is the covisibility stage (:145-197, :259-309) over the lists of one query.  It is a host-only function: no
+ * device, no handle.  neigh[i*10 .. i*10 + neigh_n[i]) are the ids of share_id[i]->GetBestCovisibilityKeyFrames(10), in its order;
+ * they are read only for the entries with share_words[i] > min_common_words (neigh_n may be anything elsewhere).  All arithmetic
+ * is float.  mode 1: the entries with share_score >= min_score are retained; a neighbour contributes when it is in the list with
+ * words > min_common_words; bestAccScore starts at min_score.  mode 0 (min_score is ignored): every scored entry is retained; a
+ * neighbour contributes when it is in the list at all, with its share_score; bestAccScore starts at 0.  Both: accScore >
+ * bestAccScore and neighbour score > bestScore are strict; an entry's pBestKF becomes a candidate when its accScore > 0.75f *
+ * bestAccScore; a pBestKF already among the candidates is dropped, the first occurrence keeps its place.  cand_out has room for
+ * nshare ids.  PS_ERR_INVALID: a null argument, a neigh_n outside 0 .. 10 where it is read. */
+typedef struct ps_kfdb ps_kfdb;
+int ps_kfdb_create(int device, int capacity, int max_words, ps_kfdb** out);
+void ps_kfdb_destroy(ps_kfdb* db);
+int ps_kfdb_add(ps_kfdb* db, ps_matcher* m, const int64_t* ids, const int32_t* const* bow_id, const double* const* bow_val,
+                const int32_t* bow_n, int n, int32_t* stored);
+int ps_kfdb_erase(ps_kfdb* db, const int64_t* ids, int n);
+int ps_kfdb_clear(ps_kfdb* db);
+int ps_kfdb_size(const ps_kfdb* db, int32_t* size);
+typedef struct ps_kfdb_query_problem {
+  int32_t n;                 /* the query's BowVector */
+  const int32_t* bow_id;
+  const double* bow_val;
+  int32_t mode;              /* 0 relocalisation, 1 loop */
+  int32_t nexcluded;         /* mode 1 */
+  const int64_t* excluded;
+  int64_t* share_id;         /* out [ps_kfdb_size] */
+  int32_t* share_words;      /* out [ps_kfdb_size] */
+  float* share_score;        /* out [ps_kfdb_size] */
+  int32_t nshare;            /* out */
+  int32_t min_common_words;  /* out */
+} ps_kfdb_query_problem;
+int ps_kfdb_query(ps_kfdb* db, ps_matcher* m, ps_kfdb_query_problem* probs, int nprob);
+int ps_kfdb_score(ps_kfdb* db, ps_matcher* m, const int32_t* bow_id, const double* bow_val, int bow_n, const int64_t* ids, int n,
+                  double* out);
+int ps_kfdb_select(int mode, float min_score, const int64_t* share_id, const int32_t* share_words, const float* share_score,
+                   int nshare, int min_common_words, const int64_t* neigh, const int32_t* neigh_n, int64_t* cand_out, int32_t* ncand);
+
 
 /* ------------------------------------------------------------------------------------------------
  * Optimiser — replaces the hot static members of ORB_SLAM2::Optimizer

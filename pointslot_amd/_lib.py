@@ -99,3 +99,26 @@ class PinnedBuffer:
             self.close()
         except Exception:
             pass
+
+
+class _KfdbQueryProblem(ctypes.Structure):
+    """ps_kfdb_query_problem"""
+    _fields_ = [("n", ctypes.c_int32), ("bow_id", ctypes.c_void_p), ("bow_val", ctypes.c_void_p), ("mode", ctypes.c_int32),
+                ("nexcluded", ctypes.c_int32), ("excluded", ctypes.c_void_p), ("share_id", ctypes.c_void_p), ("share_words", ctypes.c_void_p),
+                ("share_score", ctypes.c_void_p), ("nshare", ctypes.c_int32), ("min_common_words", ctypes.c_int32)]
+
+
+# the keyframe database (pointslot_amd/kfdb.py)
+lib.ps_kfdb_create.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
+lib.ps_kfdb_destroy.argtypes = [ctypes.c_void_p]
+lib.ps_kfdb_destroy.restype = None
+lib.ps_kfdb_add.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
+                            ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+lib.ps_kfdb_erase.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+lib.ps_kfdb_clear.argtypes = [ctypes.c_void_p]
+lib.ps_kfdb_size.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)]
+lib.ps_kfdb_query.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(_KfdbQueryProblem), ctypes.c_int]
+lib.ps_kfdb_score.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
+                              ctypes.c_void_p]
+lib.ps_kfdb_select.argtypes = [ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)]

@@ -46,6 +46,7 @@ class ORBVocabulary {
   }
   bool empty() const { return size() == 0; }
   const ps_vocabulary* handle() const { return v_; }
+  int device() const { return device_; }
 
   // transform(features, BowVector&, FeatureVector&, levelsup) (:1133-1200).  features: one 1 x 32 CV_8U row per keypoint
   // (Converter::toDescriptorVector), or the descriptor matrix itself.  matcher: the handle whose stream runs the call; nullptr:
