@@ -12,6 +12,7 @@
 #include "match_plan.h"
 #include "matcher_host.h"
 #include "tri_plan.h"
+#include "kfsearch_plan.h"
 #include "ps_common.h"
 
 extern "C" {
@@ -827,4 +828,350 @@ int ps_create_new_map_points_frames(ps_matcher* m, ps_tri_problem* probs, ps_fra
   return create_new_map_points(m, probs, kf1_frames, nprob);
 }
 
+}  // extern "C"
+
+// ---- The loop-closure and relocalisation projection matchers: ps_kf_search, ps_search_by_sim3 (kfsearch_kernels.hip) ----
+extern "C" void psk_ks_launch(const KsArrays*, int, int, int, int, hipStream_t);
+
+namespace {
+// one search as the caller described it: a ps_kf_search problem, or one direction of a ps_search_by_sim3 problem
+struct KsHostJob {
+  const ps_proj_train* T = nullptr;
+  ps_frame* frame = nullptr;
+  int kind = 0, nq = 0;
+  const uint8_t* q_valid = nullptr;
+  const uint8_t* q_already = nullptr;   // Sim3: valid = has_point && !already
+  const float* q_pos = nullptr; const float* q_normal = nullptr; const float* q_min = nullptr; const float* q_max = nullptr;
+  const uint8_t* q_desc = nullptr; const float* q_angle = nullptr;
+  const float* R = nullptr; const float* t = nullptr; const float* ow = nullptr; const float* R2 = nullptr; const float* t2 = nullptr;
+  float fx = 0, fy = 0, cx = 0, cy = 0;
+  const float* bounds = nullptr; const float* scale = nullptr;
+  float log_scale = 0, th = 0;
+  int n_levels = 0, th_dist = 0, check_ori = 0;
+  bool skip = false;                    // beyond the limits: not served
+  int status = 0;                       // out: 0 served, 1 capacity, 2 the frame handle does not hold the frame described
+  size_t t_off = 0, q_off = 0;          // out: where its results are in the buffers of KsOut
+  int nmatch = 0;                       // out (ordered kinds)
+};
+struct KsOut { const int32_t* best_idx; const int32_t* best_dist; const int32_t* match; const int32_t* match12; const int32_t* nfound; };
+
+bool ks_ordered(int kind) { return kind == 0 || kind == 2; }
+
+// Packs, uploads, launches and reads back one batch of searches.  npair > 0: jobs 2p, 2p + 1 are the two directions of Sim3 problem p.
+// The handle's lock is held by the caller; `out` points into the pinned staging buffer and is valid until the handle's next call.
+int ks_run(ps_matcher* m, std::vector<KsHostJob>& jobs, int npair, const char* what, KsOut& out) {
+  const int nj = (int)jobs.size();
+  const int NCELL = PS_GRID_COLS * PS_GRID_ROWS;
+  std::vector<ps_frame*> fr(nj, nullptr);
+  for (int j = 0; j < nj; j++) fr[j] = jobs[j].skip ? nullptr : jobs[j].frame;
+  FrameUse U;
+  int frc = frame_use_init(U, m, fr.data(), nj, what);
+  if (frc != PS_OK) return frc;
+  size_t NT = 0, NQ = 0, NQO = 0;
+  int max_nq = 1, any_ordered = 0;
+  for (int j = 0; j < nj; j++) {
+    KsHostJob& J = jobs[j];
+    J.t_off = NT; J.q_off = NQ;
+    if (J.skip) continue;
+    if (U.of[j] && (frc = frame_use_check(U, j, J.T->n, what)) != PS_OK) return frc;
+    NT += J.T->n; NQ += J.nq;
+    if (ks_ordered(J.kind)) { NQO += J.nq; any_ordered = 1; }
+    max_nq = std::max(max_nq, J.nq);
+  }
+  size_t off = 0;
+  auto take = [&](size_t bytes) { size_t r = off; off += al(bytes + 64); return r; };
+  const size_t o_job = take(sizeof(KsJob) * nj), o_pair = take(sizeof(KsPair) * (npair > 0 ? npair : 1));
+  const size_t o_tx = take(NT * 4), o_ty = take(NT * 4), o_toct = take(NT * 4), o_tang = take(NT * 4), o_tur = take(NT * 4), o_tdesc = take(NT * 32);
+  const size_t o_coff = take((size_t)nj * (NCELL + 1) * 4), o_cidx = take(NT * 4);
+  const size_t o_tocc = take(NT);
+  const size_t o_qvalid = take(NQ), o_qpos = take(NQ * 12), o_qnor = take(NQ * 12), o_qmin = take(NQ * 4), o_qmax = take(NQ * 4), o_qdesc = take(NQ * 32);
+  const size_t o_qang = take(NQ * 4);
+  const size_t o_fjobs = U.any() ? take(sizeof(FrameStageJob) * nj) : 0;
+  const size_t in_bytes = off;
+  const size_t o_bi = take(NQ * 4), o_bd = take(NQ * 4), o_match = take(NT * 4), o_m12 = take(NQ * 4), o_nm = take((size_t)nj * 4), o_ovf = take((size_t)nj * 4);
+  const size_t o_nf = take((size_t)(npair > 0 ? npair : 1) * 4), o_fst = take((size_t)nj * 4);
+  const size_t out_end = off;
+  const size_t o_cand = take(NQO * PS_KS_CAP * 4), o_ncand = take(NQ * 4), o_qtop = take(NQ * 4);
+  int rc = ensure(m, off);
+  if (rc != PS_OK) return rc;
+  uint8_t* H = m->h_buf;
+  uint8_t* D = m->d_buf;
+  memset(H, 0, in_bytes);
+  memset(H + o_fst, 0, (size_t)nj * 4);
+  KsJob* hj = (KsJob*)(H + o_job);
+  size_t c0 = 0;
+  U.all_staged = U.any();
+  for (int j = 0; j < nj; j++) {
+    const KsHostJob& J = jobs[j];
+    KsJob& d = hj[j];
+    d.kind = J.kind; d.grid_off = j * (NCELL + 1); d.t_off = (int32_t)J.t_off; d.q_off = (int32_t)J.q_off; d.cap = PS_KS_CAP;
+    if (J.skip) continue;               // nt = nq = 0: nothing is launched for it
+    const ps_proj_train& T = *J.T;
+    const size_t t0 = J.t_off, q0 = J.q_off;
+    d.nt = T.n; d.nq = J.nq;
+    d.min_x = T.min_x; d.min_y = T.min_y; d.gw_inv = T.grid_w_inv; d.gh_inv = T.grid_h_inv;
+    if (U.of[j]) { const float* g = &U.grid[(size_t)j * 4]; d.min_x = g[0]; d.min_y = g[1]; d.gw_inv = g[2]; d.gh_inv = g[3]; }
+    if (ks_ordered(J.kind)) { d.c_off = (int32_t)c0; c0 += J.nq; }
+    memcpy(d.R, J.R, 36); memcpy(d.t, J.t, 12);
+    if (J.ow) memcpy(d.ow, J.ow, 12);
+    if (J.R2) { memcpy(d.R2, J.R2, 36); memcpy(d.t2, J.t2, 12); }
+    d.fx = J.fx; d.fy = J.fy; d.cx = J.cx; d.cy = J.cy;
+    memcpy(d.bounds, J.bounds, 16); memcpy(d.scale, J.scale, 32);
+    d.log_scale = J.log_scale; d.n_levels = J.n_levels; d.th = J.th; d.th_dist = J.th_dist; d.check_ori = J.check_ori;
+    if (U.of[j] && T.n > 0) {
+      U.jobs.push_back(FrameStageJob{U.of[j]->slab, T.n, (int32_t)t0, d.grid_off, j});
+    } else if (U.any()) {
+      U.all_staged = false;
+    }
+    if (T.n > 0) {
+      const size_t n = (size_t)T.n;
+      if (!U.of[j]) {
+        const size_t filled = std::min((size_t)T.cell_off[NCELL], n);
+        memcpy(H + o_tx + t0 * 4, T.x, n * 4); memcpy(H + o_ty + t0 * 4, T.y, n * 4);
+        memcpy(H + o_toct + t0 * 4, T.octave, n * 4); memcpy(H + o_tdesc + t0 * 32, T.desc, n * 32);
+        if (T.angle) memcpy(H + o_tang + t0 * 4, T.angle, n * 4);
+        memcpy(H + o_coff + (size_t)d.grid_off * 4, T.cell_off, (size_t)(NCELL + 1) * 4);
+        memcpy(H + o_cidx + t0 * 4, T.cell_idx, filled * 4);
+      }
+      if (ks_ordered(J.kind)) memcpy(H + o_tocc + t0, T.occupied, n);
+    }
+    if (J.nq > 0) {
+      const size_t n = (size_t)J.nq;
+      if (J.q_already) {
+        uint8_t* v = H + o_qvalid + q0;
+        for (size_t i = 0; i < n; i++) v[i] = J.q_valid[i] && !J.q_already[i];
+      } else {
+        memcpy(H + o_qvalid + q0, J.q_valid, n);
+      }
+      memcpy(H + o_qpos + q0 * 12, J.q_pos, n * 12); memcpy(H + o_qmin + q0 * 4, J.q_min, n * 4);
+      memcpy(H + o_qmax + q0 * 4, J.q_max, n * 4); memcpy(H + o_qdesc + q0 * 32, J.q_desc, n * 32);
+      if (J.q_normal) memcpy(H + o_qnor + q0 * 12, J.q_normal, n * 12);
+      if (J.q_angle) memcpy(H + o_qang + q0 * 4, J.q_angle, n * 4);
+    }
+  }
+  KsPair* hp = (KsPair*)(H + o_pair);
+  for (int p = 0; p < npair; p++) {
+    const KsHostJob& a = jobs[2 * p];
+    const KsHostJob& b = jobs[2 * p + 1];
+    hp[p] = a.skip ? KsPair{0, 0, 0, 0} : KsPair{(int32_t)a.q_off, a.nq, (int32_t)b.q_off, b.nq};
+  }
+  if (U.any() && !U.jobs.empty()) memcpy(H + o_fjobs, U.jobs.data(), sizeof(FrameStageJob) * U.jobs.size());
+  if (U.all_staged) {   // everything but the searched sides' arrays and grids
+    PS_HIP(hipMemcpyAsync(D, H, o_tx, hipMemcpyHostToDevice, m->stream));
+    PS_HIP(hipMemcpyAsync(D + o_tocc, H + o_tocc, in_bytes - o_tocc, hipMemcpyHostToDevice, m->stream));
+  } else {
+    PS_HIP(hipMemcpyAsync(D, H, in_bytes, hipMemcpyHostToDevice, m->stream));
+  }
+  PS_HIP(hipMemsetAsync(D + o_nm, 0, out_end - o_nm, m->stream));   // nmatch, overflow, nfound, frame status
+  if (U.any()) {
+    FrameStageDst dst{(float*)(D + o_tx), (float*)(D + o_ty), (int32_t*)(D + o_toct), (float*)(D + o_tang), (float*)(D + o_tur), D + o_tdesc,
+                      (int32_t*)(D + o_coff), (int32_t*)(D + o_cidx), (int32_t*)(D + o_fst)};
+    if ((frc = frame_use_stage(U, m, (const FrameStageJob*)(D + o_fjobs), dst)) != PS_OK) return frc;
+  }
+  KsArrays A;
+  A.job = (const KsJob*)(D + o_job);
+  A.tx = (const float*)(D + o_tx); A.ty = (const float*)(D + o_ty); A.toct = (const int32_t*)(D + o_toct); A.tang = (const float*)(D + o_tang);
+  A.tdesc = D + o_tdesc; A.tocc = D + o_tocc; A.cell_off = (const int32_t*)(D + o_coff); A.cell_idx = (const int32_t*)(D + o_cidx);
+  A.qvalid = D + o_qvalid; A.qpos = (const float*)(D + o_qpos); A.qnormal = (const float*)(D + o_qnor); A.qmin = (const float*)(D + o_qmin);
+  A.qmax = (const float*)(D + o_qmax); A.qdesc = D + o_qdesc; A.qang = (const float*)(D + o_qang);
+  A.best_idx = (int32_t*)(D + o_bi); A.best_dist = (int32_t*)(D + o_bd);
+  A.cand = (uint32_t*)(D + o_cand); A.ncand = (int32_t*)(D + o_ncand); A.qtop = (uint32_t*)(D + o_qtop);
+  A.match = (int32_t*)(D + o_match); A.nmatch = (int32_t*)(D + o_nm); A.overflow = (int32_t*)(D + o_ovf);
+  A.pair = (const KsPair*)(D + o_pair); A.match12 = (int32_t*)(D + o_m12); A.nfound = (int32_t*)(D + o_nf);
+  hipEventRecord(m->ev0, m->stream);
+  psk_ks_launch(&A, nj, max_nq, any_ordered, npair, m->stream);
+  hipEventRecord(m->ev1, m->stream);
+  PS_HIP(hipGetLastError());
+  PS_HIP(hipMemcpyAsync(H + o_bi, D + o_bi, out_end - o_bi, hipMemcpyDeviceToHost, m->stream));
+  PS_HIP(hipStreamSynchronize(m->stream));
+  hipEventElapsedTime(&m->last_kernel_ms, m->ev0, m->ev1);
+  const int32_t* ovf = (const int32_t*)(H + o_ovf);
+  const int32_t* nm = (const int32_t*)(H + o_nm);
+  const int32_t* fst = (const int32_t*)(H + o_fst);
+  // An order-dependent job in which a point kept more than PS_KS_CAP candidates runs again with rows of PS_KS_CAP_WIDE in a store
+  // of its own; the others keep their results.  One that overflows that too is the only one that fails.
+  std::vector<int> wide;
+  for (int j = 0; j < nj; j++) {
+    KsHostJob& J = jobs[j];
+    J.status = J.skip ? 1 : (U.any() && fst[j]) ? 2 : 0;
+    J.nmatch = nm[j];
+    if (J.status == 0 && ovf[j] > 0) wide.push_back(j);
+  }
+  if (!wide.empty()) {
+    std::vector<KsJob> sub(wide.size());
+    size_t nq2 = 0;
+    int max_nq2 = 1;
+    for (size_t i = 0; i < wide.size(); i++) {
+      sub[i] = hj[wide[i]];
+      sub[i].c_off = (int32_t)nq2; sub[i].cap = PS_KS_CAP_WIDE;
+      nq2 += sub[i].nq;
+      max_nq2 = std::max(max_nq2, sub[i].nq);
+    }
+    size_t woff = 0;
+    auto wtake = [&](size_t bytes) { size_t r = woff; woff += al(bytes + 64); return r; };
+    const size_t w_job = wtake(sizeof(KsJob) * sub.size()), w_nm = wtake(sub.size() * 4), w_ovf = wtake(sub.size() * 4), w_cand = wtake(nq2 * PS_KS_CAP_WIDE * 4);
+    if (woff > m->d_wide_bytes) {
+      if (m->d_wide) hipFree(m->d_wide);
+      m->d_wide = nullptr; m->d_wide_bytes = 0;
+      PS_HIP(hipMalloc(&m->d_wide, woff));
+      m->d_wide_bytes = woff;
+    }
+    uint8_t* Wd = m->d_wide;
+    PS_HIP(hipMemcpyAsync(Wd + w_job, sub.data(), sizeof(KsJob) * sub.size(), hipMemcpyHostToDevice, m->stream));
+    PS_HIP(hipMemsetAsync(Wd + w_nm, 0, w_cand - w_nm, m->stream));
+    KsArrays A2 = A;
+    A2.job = (const KsJob*)(Wd + w_job); A2.cand = (uint32_t*)(Wd + w_cand); A2.nmatch = (int32_t*)(Wd + w_nm); A2.overflow = (int32_t*)(Wd + w_ovf);
+    psk_ks_launch(&A2, (int)sub.size(), max_nq2, 1, 0, m->stream);
+    PS_HIP(hipGetLastError());
+    std::vector<int32_t> nm2(sub.size(), 0), ovf2(sub.size(), 0);
+    PS_HIP(hipMemcpyAsync(H + o_match, D + o_match, NT * 4, hipMemcpyDeviceToHost, m->stream));
+    PS_HIP(hipStreamSynchronize(m->stream));
+    PS_HIP(hipMemcpy(nm2.data(), Wd + w_nm, sub.size() * 4, hipMemcpyDeviceToHost));
+    PS_HIP(hipMemcpy(ovf2.data(), Wd + w_ovf, sub.size() * 4, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < wide.size(); i++) {
+      jobs[wide[i]].nmatch = nm2[i];
+      if (ovf2[i] > 0) jobs[wide[i]].status = 1;
+    }
+  }
+  out.best_idx = (const int32_t*)(H + o_bi); out.best_dist = (const int32_t*)(H + o_bd); out.match = (const int32_t*)(H + o_match);
+  out.match12 = (const int32_t*)(H + o_m12); out.nfound = (const int32_t*)(H + o_nf);
+  return PS_OK;
+}
+
+int ks_bad_train(const ps_proj_train& T, bool framed, bool need_occ, bool need_angle) {
+  if (T.n < 0) return 1;
+  if (T.n == 0 || T.n > PS_KS_MAX_N) return 0;
+  if (need_occ && !T.occupied) return 1;
+  if (framed) return 0;
+  if (!T.x || !T.y || !T.octave || !T.desc || !T.cell_off || !T.cell_idx) return 1;
+  if (need_angle && !T.angle) return 1;
+  return 0;
+}
+
+// what the two calls report once every job has been served or has failed
+int ks_report(const std::vector<KsHostJob>& jobs, int per_problem, const char* what) {
+  int stale = -1, failed = -1;
+  for (size_t j = 0; j < jobs.size(); j++) {
+    if (jobs[j].status == 2 && stale < 0) stale = (int)j / per_problem;
+    if (jobs[j].status == 1 && failed < 0) failed = (int)j / per_problem;
+  }
+  if (stale >= 0)
+    return ps_set_error(PS_ERR_INVALID, "%s problem %d: the frame handle does not hold the keypoints it was published with "
+                        "(the extractor's count differed from the n given to ps_frame_publish_orb)", what, stale);
+  if (failed >= 0)
+    return ps_set_error(PS_ERR_CAPACITY, "%s problem %d: more than %d features in the searched side, more than %d points, or a point "
+                        "with more than %d candidates it could take", what, failed, PS_KS_MAX_N, PS_KS_MAX_NQ, PS_KS_CAP_WIDE);
+  return PS_OK;
+}
+
+int kf_search(ps_matcher* m, ps_kf_search_problem* probs, ps_frame* const* frames, int nprob) {
+  if (!m || nprob < 0 || (nprob > 0 && !probs)) return ps_set_error(PS_ERR_INVALID, "ps_kf_search: bad argument");
+  if (nprob == 0) return PS_OK;
+  std::lock_guard<std::mutex> lock(m->mu);
+  PS_HIP(hipSetDevice(m->device));
+  std::vector<KsHostJob> jobs(nprob);
+  for (int p = 0; p < nprob; p++) {
+    const ps_kf_search_problem& P = probs[p];
+    KsHostJob& J = jobs[p];
+    if (P.mode < 0 || P.mode > 2) return ps_set_error(PS_ERR_INVALID, "kf_search problem %d: mode must be 0, 1 or 2", p);
+    const bool ord = P.mode != 1, ori = P.mode == 2 && P.check_orientation;
+    J.frame = frames ? frames[p] : nullptr;
+    if (P.nq < 0 || ks_bad_train(P.train, J.frame != nullptr, ord, ori))
+      return ps_set_error(PS_ERR_INVALID, "kf_search problem %d: bad searched side (occupied stays a host array)", p);
+    if (P.nq > 0 && (!P.q_valid || !P.q_pos || !P.q_min_dist || !P.q_max_dist || !P.q_desc || (P.mode != 2 && !P.q_normal) || (ori && !P.q_angle)))
+      return ps_set_error(PS_ERR_INVALID, "kf_search problem %d: null query arrays", p);
+    if (ord ? (P.train.n > 0 && !P.match_of_train) : (P.nq > 0 && (!P.best_idx || !P.best_dist)))
+      return ps_set_error(PS_ERR_INVALID, "kf_search problem %d: null output arrays", p);
+    if (P.n_levels < 1 || P.n_levels > 8) return ps_set_error(PS_ERR_INVALID, "kf_search problem %d: n_levels must be 1..8", p);
+    if (P.mode == 2 && (P.th_dist < 0 || P.th_dist > 255)) return ps_set_error(PS_ERR_INVALID, "kf_search problem %d: th_dist must be 0..255", p);
+    J.T = &P.train; J.kind = P.mode; J.nq = P.nq;
+    J.q_valid = P.q_valid; J.q_pos = P.q_pos; J.q_normal = P.mode != 2 ? P.q_normal : nullptr; J.q_min = P.q_min_dist; J.q_max = P.q_max_dist;
+    J.q_desc = P.q_desc; J.q_angle = ori ? P.q_angle : nullptr;
+    J.R = P.rcw; J.t = P.tcw; J.ow = P.ow;
+    J.fx = P.fx; J.fy = P.fy; J.cx = P.cx; J.cy = P.cy; J.bounds = P.bounds; J.scale = P.scale_factors;
+    J.log_scale = P.log_scale_factor; J.n_levels = P.n_levels; J.th = P.th;
+    J.th_dist = P.mode == 2 ? P.th_dist : 50;   // TH_LOW
+    J.check_ori = ori ? 1 : 0;
+    J.skip = P.train.n > PS_KS_MAX_N || P.nq > PS_KS_MAX_NQ;
+  }
+  KsOut O;
+  int rc = ks_run(m, jobs, 0, "kf_search", O);
+  if (rc != PS_OK) return rc;
+  for (int p = 0; p < nprob; p++) {
+    ps_kf_search_problem& P = probs[p];
+    const KsHostJob& J = jobs[p];
+    if (J.status) { P.nmatches = -1; continue; }
+    if (P.mode == 1) {
+      int nf = 0;
+      if (P.nq > 0) {
+        memcpy(P.best_idx, O.best_idx + J.q_off, (size_t)P.nq * 4);
+        memcpy(P.best_dist, O.best_dist + J.q_off, (size_t)P.nq * 4);
+        for (int i = 0; i < P.nq; i++) nf += P.best_idx[i] >= 0;
+      }
+      P.nmatches = nf;
+    } else {
+      if (P.train.n > 0) memcpy(P.match_of_train, O.match + J.t_off, (size_t)P.train.n * 4);
+      P.nmatches = J.nmatch;
+    }
+  }
+  return ks_report(jobs, 1, "kf_search");
+}
+
+int search_by_sim3(ps_matcher* m, ps_sim3_problem* probs, ps_frame* const* frames1, ps_frame* const* frames2, int nprob) {
+  if (!m || nprob < 0 || (nprob > 0 && !probs)) return ps_set_error(PS_ERR_INVALID, "ps_search_by_sim3: bad argument");
+  if (nprob == 0) return PS_OK;
+  std::lock_guard<std::mutex> lock(m->mu);
+  PS_HIP(hipSetDevice(m->device));
+  std::vector<KsHostJob> jobs((size_t)2 * nprob);
+  for (int p = 0; p < nprob; p++) {
+    const ps_sim3_problem& P = probs[p];
+    const ps_sim3_side* S[2] = {&P.kf1, &P.kf2};
+    ps_frame* F[2] = {frames1 ? frames1[p] : nullptr, frames2 ? frames2[p] : nullptr};
+    for (int s = 0; s < 2; s++) {
+      const ps_sim3_side& K = *S[s];
+      if (ks_bad_train(K.train, F[s] != nullptr, false, false)) return ps_set_error(PS_ERR_INVALID, "sim3 problem %d: bad features of keyframe %d", p, s + 1);
+      if (K.train.n > 0 && (!K.has_point || !K.pos || !K.min_dist || !K.max_dist || !K.point_desc || !K.already))
+        return ps_set_error(PS_ERR_INVALID, "sim3 problem %d: null map-point arrays of keyframe %d", p, s + 1);
+      if (K.n_levels < 1 || K.n_levels > 8) return ps_set_error(PS_ERR_INVALID, "sim3 problem %d: n_levels must be 1..8", p);
+    }
+    if (P.kf1.train.n > 0 && !P.match12) return ps_set_error(PS_ERR_INVALID, "sim3 problem %d: null match12", p);
+    const bool skip = P.kf1.train.n > PS_KS_MAX_N || P.kf2.train.n > PS_KS_MAX_N;
+    for (int s = 0; s < 2; s++) {       // direction s: the points of keyframe s + 1 into the features of the other one
+      const ps_sim3_side& Q = *S[s];
+      const ps_sim3_side& T = *S[1 - s];
+      KsHostJob& J = jobs[(size_t)2 * p + s];
+      J.T = &T.train; J.frame = F[1 - s]; J.kind = 3; J.nq = Q.train.n;
+      J.q_valid = Q.has_point; J.q_already = Q.already; J.q_pos = Q.pos; J.q_min = Q.min_dist; J.q_max = Q.max_dist; J.q_desc = Q.point_desc;
+      J.R = Q.rcw; J.t = Q.tcw; J.R2 = s == 0 ? P.sr21 : P.sr12; J.t2 = s == 0 ? P.t21 : P.t12;
+      J.fx = P.fx; J.fy = P.fy; J.cx = P.cx; J.cy = P.cy;
+      J.bounds = T.bounds; J.scale = T.scale_factors; J.log_scale = T.log_scale_factor; J.n_levels = T.n_levels;
+      J.th = P.th; J.th_dist = 100;     // TH_HIGH
+      J.skip = skip;
+    }
+  }
+  KsOut O;
+  int rc = ks_run(m, jobs, nprob, "sim3", O);
+  if (rc != PS_OK) return rc;
+  for (int p = 0; p < nprob; p++) {
+    ps_sim3_problem& P = probs[p];
+    KsHostJob& a = jobs[(size_t)2 * p];
+    KsHostJob& b = jobs[(size_t)2 * p + 1];
+    if (a.status || b.status) { a.status = b.status = std::max(a.status, b.status); P.nfound = -1; continue; }
+    const size_t n1 = (size_t)P.kf1.train.n, n2 = (size_t)P.kf2.train.n;
+    if (n1 > 0) memcpy(P.match12, O.match12 + a.q_off, n1 * 4);
+    if (n1 > 0 && P.match1) memcpy(P.match1, O.best_idx + a.q_off, n1 * 4);
+    if (n2 > 0 && P.match2) memcpy(P.match2, O.best_idx + b.q_off, n2 * 4);
+    P.nfound = O.nfound[p];
+  }
+  return ks_report(jobs, 2, "sim3");
+}
+}  // namespace
+
+extern "C" {
+int ps_kf_search(ps_matcher* m, ps_kf_search_problem* probs, int nprob) { return kf_search(m, probs, nullptr, nprob); }
+int ps_kf_search_frames(ps_matcher* m, ps_kf_search_problem* probs, ps_frame* const* frames, int nprob) { return kf_search(m, probs, frames, nprob); }
+int ps_search_by_sim3(ps_matcher* m, ps_sim3_problem* probs, int nprob) { return search_by_sim3(m, probs, nullptr, nullptr, nprob); }
+int ps_search_by_sim3_frames(ps_matcher* m, ps_sim3_problem* probs, ps_frame* const* frames1, ps_frame* const* frames2, int nprob) {
+  return search_by_sim3(m, probs, frames1, frames2, nprob);
+}
 }  // extern "C"

@@ -5,7 +5,9 @@
 // take the ps_*_problem structs directly for callers that already keep their data as arrays.
 #pragma once
 #include <algorithm>
+#include <cmath>
 #include <cstring>
+#include <set>
 #include <stdexcept>
 #include <string>
 #include <type_traits>
@@ -110,6 +112,53 @@ class ORBmatcher {
     int total = 0;
     for (int i = 0; i < n; i++) total += p[i].nmatches;
     return total;
+  }
+  // the loop-closure / relocalisation projection matchers on caller-filled problems (include/pointslot_hip.h: ps_kf_search_problem;
+  // mode, th_dist and check_orientation are the caller's, so one call may mix the three members).  frames: nullptr, or per problem
+  // the frame handle the searched side comes from.  Returns the summed match count.
+  int KfSearchBatch(ps_kf_search_problem* p, ps_frame* const* frames, int n) {
+    if (n <= 0) return 0;
+    if ((frames ? ps_kf_search_frames(h_, p, frames, n) : ps_kf_search(h_, p, n)) != PS_OK) throw std::runtime_error(ps_last_error());
+    int total = 0;
+    for (int i = 0; i < n; i++) total += p[i].nmatches;
+    return total;
+  }
+  // SearchBySim3 on caller-filled problems (ps_sim3_problem); frames1 / frames2: nullptr, or per problem the handles of keyframe 1 / 2
+  int SearchBySim3Batch(ps_sim3_problem* p, ps_frame* const* frames1, ps_frame* const* frames2, int n) {
+    if (n <= 0) return 0;
+    if (((frames1 || frames2) ? ps_search_by_sim3_frames(h_, p, frames1, frames2, n) : ps_search_by_sim3(h_, p, n)) != PS_OK) throw std::runtime_error(ps_last_error());
+    int total = 0;
+    for (int i = 0; i < n; i++) total += p[i].nfound;
+    return total;
+  }
+  // The decomposition of a Sim3 pose at ORBmatcher.cc:422-426 / :1271-1275 as ONE stated model (cv::MatExpr division by a scalar is
+  // OpenCV-internal): the dot product of row 0 in double, scw = its root rounded to float, every entry of Rcw and tcw =
+  // float(double(entry) * (1.0 / double(scw))), Ow = -Rcw^T tcw with the products and their sum in double, rounded once.
+  // (pointslot_amd.matcher.decompose_scw is the same model.)
+  template <class MatT> static void DecomposeScw(const MatT& Scw, float rcw[9], float tcw[3], float ow[3]) {
+    double dot = 0.0;
+    for (int c = 0; c < 3; c++) dot += (double)Scw.template at<float>(0, c) * (double)Scw.template at<float>(0, c);
+    const float scw = (float)std::sqrt(dot);
+    const double inv = 1.0 / (double)scw;
+    for (int r = 0; r < 3; r++) {
+      for (int c = 0; c < 3; c++) rcw[3 * r + c] = (float)((double)Scw.template at<float>(r, c) * inv);
+      tcw[r] = (float)((double)Scw.template at<float>(r, 3) * inv);
+    }
+    for (int r = 0; r < 3; r++) ow[r] = (float)(-((double)rcw[r] * (double)tcw[0] + (double)rcw[3 + r] * (double)tcw[1] + (double)rcw[6 + r] * (double)tcw[2]));
+  }
+  // sR12 = s12 * R12, sR21 = (1.0 / s12) * R12.t(), t21 = -sR21 * t12 (ORBmatcher.cc:1404-1406) as ONE stated model: every entry of
+  // sR12 = float(double(R12) * double(s12)), of sR21 = float(double(R12^T) * (1.0 / double(s12))), t21 with the products and their
+  // sum in double, negated, rounded once.  (pointslot_amd.matcher.sim3_pair is the same model.)
+  template <class MatT> static void Sim3Pair(float s12, const MatT& R12, const MatT& t12, float sr12[9], float t12o[3], float sr21[9], float t21[3]) {
+    const double s = (double)s12, inv = 1.0 / (double)s12;
+    for (int r = 0; r < 3; r++) {
+      for (int c = 0; c < 3; c++) {
+        sr12[3 * r + c] = (float)((double)R12.template at<float>(r, c) * s);
+        sr21[3 * r + c] = (float)((double)R12.template at<float>(c, r) * inv);
+      }
+      t12o[r] = t12.template at<float>(r);
+    }
+    for (int r = 0; r < 3; r++) t21[r] = (float)(-((double)sr21[3 * r] * (double)t12o[0] + (double)sr21[3 * r + 1] * (double)t12o[1] + (double)sr21[3 * r + 2] * (double)t12o[2]));
   }
   ps_matcher* handle() { return h_; }   // (kernel time of the last call: ps_matcher_last_kernel_ms)
   static float RadiusByViewingCos(const float& viewCos) { return viewCos > 0.998 ? 2.5f : 4.0f; }   // ORBmatcher.cc:252-258
@@ -287,6 +336,137 @@ class ORBmatcher {
     return p.nmatches;
   }
 
+  // ------------------------------------------------------------------------------------------------------------------
+  // The loop-closure and relocalisation members, over KeyFrame- / Frame- / MapPoint-shaped types (tests/cpp/loop_view.h).
+  // KeyFrame: N, mvKeysUn, mvuRight, mDescriptors, mGrid[ix][iy], mnMinX .. mnMaxY, mfGridElementWidthInv / HeightInv, fx .. cy,
+  // mvScaleFactors, mfLogScaleFactor, mnScaleLevels, GetRotation, GetTranslation, GetMapPoint, GetMapPoints, GetMapPointMatches,
+  // AddMapPoint.  MapPoint: isBad, GetWorldPos, GetNormal, GetDescriptor, AddObservation, GetIndexInKeyFrame and mfMinDistance /
+  // mfMaxDistance (protected in the reference, and Get{Min,Max}DistanceInvariance return them scaled: PredictScale needs them as
+  // they are, so a binding makes them readable).  mGrid is private in the reference's KeyFrame as well.
+  // ------------------------------------------------------------------------------------------------------------------
+
+  // int SearchByProjection(KeyFrame* pKF, cv::Mat Scw, const vector<MapPoint*> &vpPoints, vector<MapPoint*> &vpMatched, int th)   :413-526
+  template <class KeyFrameT, class MatT, class MapPointT>
+  int SearchByProjection(KeyFrameT* pKF, MatT Scw, const std::vector<MapPointT*>& vpPoints, std::vector<MapPointT*>& vpMatched, int th) {
+    TrainSide T;
+    fillKfTrain(T, *pKF);
+    for (int j = 0; j < T.n && j < (int)vpMatched.size(); j++) T.occupied[j] = vpMatched[j] ? 1 : 0;
+    std::set<MapPointT*> spAlreadyFound(vpMatched.begin(), vpMatched.end());
+    spAlreadyFound.erase(static_cast<MapPointT*>(NULL));
+    PointSide Q;
+    for (MapPointT* pMP : vpPoints) Q.add(pMP, !pMP->isBad() && !spAlreadyFound.count(pMP), true, 0.f);
+    ps_kf_search_problem p = ps_kf_search_problem{};
+    p.mode = 0;
+    DecomposeScw(Scw, p.rcw, p.tcw, p.ow);
+    std::vector<int32_t> match((std::size_t)std::max(T.n, 1), -1);
+    p.match_of_train = match.data(); p.th = (float)th;
+    runKfSearch(p, T, Q, *pKF);
+    for (int j = 0; j < T.n && j < (int)vpMatched.size(); j++)
+      if (match[j] >= 0) vpMatched[j] = vpPoints[match[j]];
+    return p.nmatches;
+  }
+
+  // int Fuse(KeyFrame* pKF, cv::Mat Scw, const vector<MapPoint*> &vpPoints, float th, vector<MapPoint*> &vpReplacePoint)            :1262-1385
+  // with the map surgery of :1369-1379 in candidate order
+  template <class KeyFrameT, class MatT, class MapPointT>
+  int Fuse(KeyFrameT* pKF, MatT Scw, const std::vector<MapPointT*>& vpPoints, float th, std::vector<MapPointT*>& vpReplacePoint) {
+    TrainSide T;
+    fillKfTrain(T, *pKF);
+    const auto spAlreadyFound = pKF->GetMapPoints();
+    PointSide Q;
+    for (MapPointT* pMP : vpPoints) Q.add(pMP, !pMP->isBad() && !spAlreadyFound.count(pMP), true, 0.f);
+    ps_kf_search_problem p = ps_kf_search_problem{};
+    p.mode = 1;
+    DecomposeScw(Scw, p.rcw, p.tcw, p.ow);
+    const int nq = (int)vpPoints.size();
+    std::vector<int32_t> bi((std::size_t)std::max(nq, 1), -1), bd((std::size_t)std::max(nq, 1), 256);
+    p.best_idx = bi.data(); p.best_dist = bd.data(); p.th = th;
+    runKfSearch(p, T, Q, *pKF);
+    int nFused = 0;
+    for (int iMP = 0; iMP < nq; iMP++) {
+      if (bi[iMP] < 0) continue;
+      MapPointT* pMP = vpPoints[iMP];
+      MapPointT* pMPinKF = pKF->GetMapPoint(bi[iMP]);
+      if (pMPinKF) {
+        if (!pMPinKF->isBad()) vpReplacePoint[iMP] = pMPinKF;
+      } else {
+        pMP->AddObservation(pKF, bi[iMP]);
+        pKF->AddMapPoint(pMP, bi[iMP]);
+      }
+      nFused++;
+    }
+    return nFused;
+  }
+
+  // int SearchByProjection(Frame &CurrentFrame, KeyFrame* pKF, const set<MapPoint*> &sAlreadyFound, const float th, const int ORBdist)   :2529-2656
+  // A Frame type with a non-null `ps_frame* mpDeviceFrame` is searched on the device: relocalisation runs this once per candidate keyframe.
+  template <class FrameT, class KeyFrameT, class MapPointT>
+  int SearchByProjection(FrameT& CurrentFrame, KeyFrameT* pKF, const std::set<MapPointT*>& sAlreadyFound, const float th, const int ORBdist) {
+    TrainSide T;
+    T.frame = deviceFrameOf(CurrentFrame);
+    if (T.frame) fillTrainOnDevice(T, (int)CurrentFrame.mvKeysUn.size());
+    else fillTrain(T, CurrentFrame.mvKeysUn, CurrentFrame.mvuRight, CurrentFrame.mDescriptors, CurrentFrame.mGrid, CurrentFrame);
+    for (std::size_t j = 0; j < CurrentFrame.mvpMapPoints.size(); j++) T.occupied[j] = CurrentFrame.mvpMapPoints[j] ? 1 : 0;
+    const auto vpMPs = pKF->GetMapPointMatches();
+    PointSide Q;
+    for (std::size_t i = 0; i < vpMPs.size(); i++) {
+      auto* pMP = vpMPs[i];
+      Q.add(pMP, pMP && !pMP->isBad() && !sAlreadyFound.count(pMP), false, pKF->mvKeysUn[i].angle);
+    }
+    ps_kf_search_problem p = ps_kf_search_problem{};
+    p.mode = 2; p.th_dist = ORBdist; p.check_orientation = mbCheckOrientation ? 1 : 0;
+    // Rcw, tcw of mTcw and Ow = -Rcw^T tcw (:2533-2535: a transposed operand, products and sum in double)
+    for (int r = 0; r < 3; r++) {
+      for (int c = 0; c < 3; c++) p.rcw[3 * r + c] = CurrentFrame.mTcw.template at<float>(r, c);
+      p.tcw[r] = CurrentFrame.mTcw.template at<float>(r, 3);
+    }
+    for (int r = 0; r < 3; r++)
+      p.ow[r] = (float)(-((double)p.rcw[r] * (double)p.tcw[0] + (double)p.rcw[3 + r] * (double)p.tcw[1] + (double)p.rcw[6 + r] * (double)p.tcw[2]));
+    std::vector<int32_t> match((std::size_t)std::max(T.n, 1), -1);
+    p.match_of_train = match.data(); p.th = th;
+    runKfSearch(p, T, Q, CurrentFrame);
+    for (int j = 0; j < T.n; j++) {
+      if (match[j] >= 0) CurrentFrame.mvpMapPoints[j] = vpMPs[match[j]];
+      else if (match[j] == -2) CurrentFrame.mvpMapPoints[j] = NULL;   // assigned, then reset by the rotation check (:2642-2652)
+    }
+    return p.nmatches;
+  }
+
+  // int SearchBySim3(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*> &vpMatches12, const float &s12, const cv::Mat &R12,
+  //                  const cv::Mat &t12, const float th)                                                                   :1387-1611
+  template <class KeyFrameT, class MapPointT, class MatT>
+  int SearchBySim3(KeyFrameT* pKF1, KeyFrameT* pKF2, std::vector<MapPointT*>& vpMatches12, const float& s12, const MatT& R12, const MatT& t12, const float th) {
+    const auto vpMapPoints1 = pKF1->GetMapPointMatches(), vpMapPoints2 = pKF2->GetMapPointMatches();
+    const int N1 = (int)vpMapPoints1.size(), N2 = (int)vpMapPoints2.size();
+    TrainSide T1, T2;
+    fillKfTrain(T1, *pKF1); fillKfTrain(T2, *pKF2);
+    PointSide Q1, Q2;
+    for (auto* pMP : vpMapPoints1) Q1.add(pMP, pMP && !pMP->isBad(), false, 0.f);
+    for (auto* pMP : vpMapPoints2) Q2.add(pMP, pMP && !pMP->isBad(), false, 0.f);
+    std::vector<uint8_t> already1((std::size_t)std::max(N1, 1), 0), already2((std::size_t)std::max(N2, 1), 0);
+    for (int i = 0; i < N1; i++) {
+      MapPointT* pMP = vpMatches12[i];
+      if (!pMP) continue;
+      already1[i] = 1;
+      const int idx2 = pMP->GetIndexInKeyFrame(pKF2);
+      if (idx2 >= 0 && idx2 < N2) already2[idx2] = 1;
+    }
+    ps_sim3_problem p = ps_sim3_problem{};
+    fillSim3Side(p.kf1, T1, Q1, already1, *pKF1);
+    fillSim3Side(p.kf2, T2, Q2, already2, *pKF2);
+    p.fx = pKF1->fx; p.fy = pKF1->fy; p.cx = pKF1->cx; p.cy = pKF1->cy;     // keyframe 1's, for both directions (:1390-1393)
+    Sim3Pair(s12, R12, t12, p.sr12, p.t12, p.sr21, p.t21);
+    p.th = th;
+    std::vector<int32_t> m12((std::size_t)std::max(N1, 1), -1);
+    p.match12 = m12.data();
+    ps_frame* f1 = deviceFrameOf(*pKF1);
+    ps_frame* f2 = deviceFrameOf(*pKF2);
+    SearchBySim3Batch(&p, f1 ? &f1 : nullptr, f2 ? &f2 : nullptr, 1);
+    for (int i1 = 0; i1 < N1; i1++)
+      if (m12[i1] >= 0) vpMatches12[i1] = vpMapPoints2[m12[i1]];
+    return p.nfound;
+  }
+
  protected:
   // one side of SearchByBoW as ps_bow_side's arrays; points == nullptr: the Frame side of the first overload
   struct BowSide {
@@ -433,6 +613,65 @@ class ORBmatcher {
     for (int j = 0; j < T.n; j++)
       if (match[j] >= 0) assign(j, pts[match[j]]);
     return n;
+  }
+
+  // the projected points of a ps_kf_search problem / the per-slot map points of a ps_sim3_side
+  struct PointSide {
+    std::vector<uint8_t> valid, desc;
+    std::vector<float> pos, normal, mind, maxd, angle;
+    template <class MapPointT> void add(MapPointT* pMP, bool ok, bool withNormal, float ang) {
+      const std::size_t i = valid.size();
+      valid.push_back(ok ? 1 : 0); angle.push_back(ang);
+      desc.resize((i + 1) * 32, 0); pos.resize((i + 1) * 3, 0.f); normal.resize((i + 1) * 3, 0.f);
+      mind.push_back(0.f); maxd.push_back(1.f);
+      if (!ok) return;
+      const pscv::Mat X = pMP->GetWorldPos();
+      for (int c = 0; c < 3; c++) pos[3 * i + c] = X.template at<float>(c);
+      if (withNormal) {
+        const pscv::Mat Pn = pMP->GetNormal();
+        for (int c = 0; c < 3; c++) normal[3 * i + c] = Pn.template at<float>(c);
+      }
+      mind[i] = pMP->mfMinDistance; maxd[i] = pMP->mfMaxDistance;
+      const pscv::Mat d = pMP->GetDescriptor();
+      std::memcpy(&desc[i * 32], d.template ptr<uint8_t>(), 32);
+    }
+    void pad() {   // (never hand out a null data() for an empty side)
+      if (valid.empty()) { valid.assign(1, 0); desc.assign(32, 0); pos.assign(3, 0.f); normal.assign(3, 0.f); mind.assign(1, 0.f); maxd.assign(1, 1.f); angle.assign(1, 0.f); }
+    }
+  };
+  // a keyframe as the searched side: on the device already (mpDeviceFrame) or packed from mvKeysUn / mDescriptors / mGrid
+  template <class KeyFrameT> static void fillKfTrain(TrainSide& T, KeyFrameT& KF) {
+    T.frame = deviceFrameOf(KF);
+    if (T.frame) fillTrainOnDevice(T, (int)KF.mvKeysUn.size()); else fillTrain(T, KF.mvKeysUn, KF.mvuRight, KF.mDescriptors, KF.mGrid, KF);
+  }
+  template <class ViewT> static void fillView(const ViewT& V, float bounds[4], float scale[8], float& logScale, int32_t& nLevels) {
+    bounds[0] = (float)V.mnMinX; bounds[1] = (float)V.mnMaxX; bounds[2] = (float)V.mnMinY; bounds[3] = (float)V.mnMaxY;
+    for (int l = 0; l < 8; l++) scale[l] = l < (int)V.mvScaleFactors.size() ? V.mvScaleFactors[l] : 1.f;
+    logScale = V.mfLogScaleFactor; nLevels = V.mnScaleLevels;
+  }
+  // V: the KeyFrame / Frame being searched into (intrinsics, bounds, scale tables)
+  template <class ViewT> void runKfSearch(ps_kf_search_problem& p, TrainSide& T, PointSide& Q, const ViewT& V) {
+    T.bind(p.train);
+    p.nq = (int)Q.valid.size();
+    Q.pad();
+    p.q_valid = Q.valid.data(); p.q_pos = Q.pos.data(); p.q_normal = Q.normal.data(); p.q_min_dist = Q.mind.data(); p.q_max_dist = Q.maxd.data();
+    p.q_desc = Q.desc.data(); p.q_angle = Q.angle.data();
+    p.fx = V.fx; p.fy = V.fy; p.cx = V.cx; p.cy = V.cy;
+    fillView(V, p.bounds, p.scale_factors, p.log_scale_factor, p.n_levels);
+    ps_frame* frame = T.frame;
+    KfSearchBatch(&p, frame ? &frame : nullptr, 1);
+  }
+  template <class KeyFrameT> static void fillSim3Side(ps_sim3_side& s, TrainSide& T, PointSide& Q, std::vector<uint8_t>& already, KeyFrameT& KF) {
+    T.bind(s.train);
+    Q.pad();
+    s.has_point = Q.valid.data(); s.pos = Q.pos.data(); s.min_dist = Q.mind.data(); s.max_dist = Q.maxd.data(); s.point_desc = Q.desc.data();
+    s.already = already.data();
+    const auto R = KF.GetRotation(), t = KF.GetTranslation();
+    for (int r = 0; r < 3; r++) {
+      for (int c = 0; c < 3; c++) s.rcw[3 * r + c] = R.template at<float>(r, c);
+      s.tcw[r] = t.template at<float>(r);
+    }
+    fillView(KF, s.bounds, s.scale_factors, s.log_scale_factor, s.n_levels);
   }
 
   int run(ps_proj_problem& p, ps_frame* frame = nullptr) {

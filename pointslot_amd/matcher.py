@@ -493,3 +493,238 @@ def _search_by_bow_one(self, a, b, mode=0):
 
 ORBmatcher.SearchByBoWBatch = _search_by_bow
 ORBmatcher.SearchByBoW = _search_by_bow_one
+
+
+# ---- the loop-closure and relocalisation projection matchers (ps_kf_search, ps_search_by_sim3) ------------------------------
+def _dot_double(a, b):
+    """cv::Mat product convention of the repository: the float products and their sum in double, rounded to float once"""
+    return np.float32(float(a[0]) * float(b[0]) + float(a[1]) * float(b[1]) + float(a[2]) * float(b[2]))
+
+
+def decompose_scw(Scw):
+    """The decomposition of a Sim3 pose at ORBmatcher.cc:422-426 / :1271-1275, as ONE stated model (cv::MatExpr division by a scalar
+    is OpenCV-internal): the dot product of row 0 in double, scw = sqrt rounded to float, every entry of Rcw and tcw =
+    float(double(entry) * (1.0 / double(scw))), Ow = -Rcw^T tcw with the products and their sum in double, rounded once.
+    -> (Rcw float32 [3, 3], tcw float32 [3], Ow float32 [3], scw float32)"""
+    S = np.asarray(Scw, np.float32).reshape(4, 4)
+    r0 = S[0, :3]
+    scw = np.float32(np.sqrt(float(r0[0]) * float(r0[0]) + float(r0[1]) * float(r0[1]) + float(r0[2]) * float(r0[2])))
+    inv = 1.0 / float(scw)
+    Rcw = (S[:3, :3].astype(np.float64) * inv).astype(np.float32)
+    tcw = (S[:3, 3].astype(np.float64) * inv).astype(np.float32)
+    Ow = np.array([np.float32(-float(_dot_double(Rcw[:, r], tcw))) for r in range(3)], np.float32)
+    return Rcw, tcw, Ow, scw
+
+
+def sim3_pair(s12, R12, t12):
+    """sR12 = s12 * R12, sR21 = (1.0 / s12) * R12.t(), t21 = -sR21 * t12 (ORBmatcher.cc:1404-1406) as ONE stated model: every entry of
+    sR12 = float(double(R12) * double(s12)), of sR21 = float(double(R12^T) * (1.0 / double(s12))), t21 with the products and their
+    sum in double, negated, rounded once.  -> (sR12, t12, sR21, t21) as float32"""
+    s = float(np.float32(s12))
+    R = np.asarray(R12, np.float32).reshape(3, 3)
+    t = np.asarray(t12, np.float32).reshape(3)
+    sR12 = (R.astype(np.float64) * s).astype(np.float32)
+    sR21 = (R.T.astype(np.float64) * (1.0 / s)).astype(np.float32)
+    t21 = np.array([np.float32(-float(_dot_double(sR21[r], t))) for r in range(3)], np.float32)
+    return sR12, t.copy(), sR21, t21
+
+
+class _KfSearchProblem(ctypes.Structure):
+    _fields_ = [("train", _ProjTrain), ("mode", ctypes.c_int32), ("nq", ctypes.c_int32), ("q_valid", ctypes.c_void_p), ("q_pos", ctypes.c_void_p),
+                ("q_normal", ctypes.c_void_p), ("q_min_dist", ctypes.c_void_p), ("q_max_dist", ctypes.c_void_p), ("q_desc", ctypes.c_void_p),
+                ("q_angle", ctypes.c_void_p), ("rcw", ctypes.c_float * 9), ("tcw", ctypes.c_float * 3), ("ow", ctypes.c_float * 3),
+                ("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float), ("bounds", ctypes.c_float * 4),
+                ("scale_factors", ctypes.c_float * 8), ("log_scale_factor", ctypes.c_float), ("n_levels", ctypes.c_int32), ("th", ctypes.c_float),
+                ("th_dist", ctypes.c_int32), ("check_orientation", ctypes.c_int32), ("match_of_train", ctypes.c_void_p),
+                ("best_idx", ctypes.c_void_p), ("best_dist", ctypes.c_void_p), ("nmatches", ctypes.c_int32)]
+
+
+class _Sim3Side(ctypes.Structure):
+    _fields_ = [("train", _ProjTrain), ("has_point", ctypes.c_void_p), ("pos", ctypes.c_void_p), ("min_dist", ctypes.c_void_p),
+                ("max_dist", ctypes.c_void_p), ("point_desc", ctypes.c_void_p), ("already", ctypes.c_void_p),
+                ("rcw", ctypes.c_float * 9), ("tcw", ctypes.c_float * 3), ("bounds", ctypes.c_float * 4), ("scale_factors", ctypes.c_float * 8),
+                ("log_scale_factor", ctypes.c_float), ("n_levels", ctypes.c_int32)]
+
+
+class _Sim3Problem(ctypes.Structure):
+    _fields_ = [("kf1", _Sim3Side), ("kf2", _Sim3Side), ("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float),
+                ("sr12", ctypes.c_float * 9), ("t12", ctypes.c_float * 3), ("sr21", ctypes.c_float * 9), ("t21", ctypes.c_float * 3),
+                ("th", ctypes.c_float), ("match12", ctypes.c_void_p), ("match1", ctypes.c_void_p), ("match2", ctypes.c_void_p),
+                ("nfound", ctypes.c_int32)]
+
+
+def _fill_kf_train(t, F, keep, need_occupied):
+    """the searched side of a ps_kf_search / ps_search_by_sim3 problem: x, y, octave, desc, cell_off, cell_idx, grid (angle, occupied
+    where the mode reads them), or "frame" = a DeviceFrame holding them (occupied stays a host array)"""
+    framed = F.get("frame") is not None
+    n = len(F["frame"]) if framed else len(F["x"])
+    a = {}
+    if not framed:
+        a.update(x=_arr(F["x"], np.float32), y=_arr(F["y"], np.float32), octave=_arr(F["octave"], np.int32),
+                 angle=_arr(F.get("angle", np.zeros(n, np.float32)), np.float32), desc=_arr(F["desc"], np.uint8).reshape(-1, 32),
+                 cell_off=_arr(F["cell_off"], np.int32), cell_idx=_arr(F["cell_idx"], np.int32))
+        t.min_x, t.min_y, t.grid_w_inv, t.grid_h_inv = [float(v) for v in F["grid"]]
+    if need_occupied:
+        a["occupied"] = _arr(F.get("occupied", np.zeros(n, np.uint8)), np.uint8)
+    if any(len(v) != n for k, v in a.items() if k not in ("cell_off", "cell_idx")):
+        raise ValueError("the arrays of a searched side differ in length")
+    keep.append(a)
+    t.n = n
+    for k, v in a.items():
+        setattr(t, k, v.ctypes.data)
+    return n
+
+
+def _c_floats(v, n):
+    return (ctypes.c_float * n)(*np.asarray(v, np.float32).reshape(n))
+
+
+def _kf_search(self, problems, partial_ok=False, mode=None):
+    """ps_kf_search for a batch.  problems: list of dicts {mode 0 / 1 / 2 (or the `mode` argument for all), train (see _fill_kf_train),
+    query {valid, pos [m, 3], normal [m, 3] (modes 0, 1), min_dist, max_dist, desc [m, 32], angle (mode 2)}, R, t, ow (decompose_scw
+    for the Sim3 overloads; GetRotation / GetTranslation / GetCameraCenter of the frame in mode 2), K4 (fx, fy, cx, cy), bounds,
+    scale_factors, log_scale_factor, n_levels, th, th_dist (mode 2: ORBdist), check_orientation (mode 2; default: the matcher's)}.
+    Returns per problem a dict: nmatches, and match_of_train int32 [n] (modes 0, 2) or best_idx / best_dist int32 [m] (mode 1);
+    nmatches = -1 marks a problem beyond the limits when partial_ok lets the call return after PS_ERR_CAPACITY."""
+    n = len(problems)
+    if n == 0:
+        return []
+    arr = (_KfSearchProblem * n)()
+    keep, outs = [], []
+    for i, pr in enumerate(problems):
+        p = arr[i]
+        p.mode = int(pr["mode"] if mode is None else mode)
+        nt = _fill_kf_train(p.train, pr["train"], keep, p.mode != 1)
+        q = pr["query"]
+        m = len(q["valid"])
+        a = dict(q_valid=_arr(q["valid"], np.uint8), q_pos=_arr(q["pos"], np.float32).reshape(-1, 3), q_min_dist=_arr(q["min_dist"], np.float32),
+                 q_max_dist=_arr(q["max_dist"], np.float32), q_desc=_arr(q["desc"], np.uint8).reshape(-1, 32))
+        if p.mode != 2:
+            a["q_normal"] = _arr(q["normal"], np.float32).reshape(-1, 3)
+        p.check_orientation = 1 if (p.mode == 2 and pr.get("check_orientation", self.mbCheckOrientation)) else 0
+        if p.check_orientation:
+            a["q_angle"] = _arr(q["angle"], np.float32)
+        if any(len(v) != m for v in a.values()):
+            raise ValueError("the arrays of a query side differ in length")
+        for k, v in a.items():
+            setattr(p, k, v.ctypes.data)
+        p.nq = m
+        p.rcw = _c_floats(pr["R"], 9); p.tcw = _c_floats(pr["t"], 3); p.ow = _c_floats(pr["ow"], 3)
+        p.fx, p.fy, p.cx, p.cy = [float(v) for v in pr["K4"]]
+        p.bounds = _c_floats(pr["bounds"], 4); p.scale_factors = _c_floats(pr["scale_factors"], 8)
+        p.log_scale_factor = float(pr["log_scale_factor"]); p.n_levels = int(pr["n_levels"]); p.th = float(pr["th"])
+        p.th_dist = int(pr.get("th_dist", ORBmatcher.TH_HIGH if p.mode == 2 else ORBmatcher.TH_LOW))
+        o = dict(match_of_train=np.full(max(nt, 1), -3, np.int32), best_idx=np.full(max(m, 1), -3, np.int32), best_dist=np.full(max(m, 1), -3, np.int32))
+        for name, v in o.items():
+            setattr(p, name, v.ctypes.data)
+        p.nmatches = -2
+        keep.append(a); outs.append((o, nt, m, p.mode))
+    fr = [pr["train"].get("frame") for pr in problems]
+    if all(f is None for f in fr):
+        rc = lib.ps_kf_search(self._h, arr, n)
+    else:
+        rc = lib.ps_kf_search_frames(self._h, arr, (ctypes.c_void_p * n)(*[None if f is None else f._h.value for f in fr]), n)
+    if not (partial_ok and rc == -3):
+        check(rc)
+    res = []
+    for i, (o, nt, m, md) in enumerate(outs):
+        r = dict(nmatches=int(arr[i].nmatches))
+        if md == 1:
+            r.update(best_idx=o["best_idx"][:m].copy(), best_dist=o["best_dist"][:m].copy())
+        else:
+            r.update(match_of_train=o["match_of_train"][:nt].copy())
+        res.append(r)
+    return res
+
+
+def _fill_sim3_side(c, kf, keep):
+    """one ps_sim3_side from a keyframe dict: the searched-side keys of _fill_kf_train plus has_point, pos [n, 3], min_dist, max_dist,
+    point_desc [n, 32], already, R, t, bounds, scale_factors, log_scale_factor, n_levels"""
+    n = _fill_kf_train(c.train, kf, keep, False)
+    a = dict(has_point=_arr(kf["has_point"], np.uint8), pos=_arr(kf["pos"], np.float32).reshape(-1, 3), min_dist=_arr(kf["min_dist"], np.float32),
+             max_dist=_arr(kf["max_dist"], np.float32), point_desc=_arr(kf["point_desc"], np.uint8).reshape(-1, 32),
+             already=_arr(kf.get("already", np.zeros(n, np.uint8)), np.uint8))
+    if any(len(v) != n for v in a.values()):
+        raise ValueError("the arrays of a keyframe differ in length")
+    keep.append(a)
+    for k, v in a.items():
+        setattr(c, k, v.ctypes.data)
+    c.rcw = _c_floats(kf["R"], 9); c.tcw = _c_floats(kf["t"], 3); c.bounds = _c_floats(kf["bounds"], 4)
+    c.scale_factors = _c_floats(kf["scale_factors"], 8)
+    c.log_scale_factor = float(kf["log_scale_factor"]); c.n_levels = int(kf["n_levels"])
+    return n
+
+
+def _search_by_sim3_batch(self, problems, partial_ok=False):
+    """ps_search_by_sim3 for a batch.  problems: list of dicts {kf1, kf2 (see _fill_sim3_side), K4 = keyframe 1's (fx, fy, cx, cy),
+    s12, R12, t12 (through sim3_pair) or sr12, t12, sr21, t21 given outright, th}.  Returns per problem a dict: nfound, match12
+    int32 [n1], match1 int32 [n1], match2 int32 [n2]; nfound = -1 marks a failed problem under partial_ok."""
+    n = len(problems)
+    if n == 0:
+        return []
+    arr = (_Sim3Problem * n)()
+    keep, outs = [], []
+    for i, pr in enumerate(problems):
+        p = arr[i]
+        n1 = _fill_sim3_side(p.kf1, pr["kf1"], keep)
+        n2 = _fill_sim3_side(p.kf2, pr["kf2"], keep)
+        p.fx, p.fy, p.cx, p.cy = [float(v) for v in pr["K4"]]
+        sr12, t12, sr21, t21 = (pr["sr12"], pr["t12"], pr["sr21"], pr["t21"]) if "sr12" in pr else sim3_pair(pr["s12"], pr["R12"], pr["t12"])
+        p.sr12 = _c_floats(sr12, 9); p.t12 = _c_floats(t12, 3); p.sr21 = _c_floats(sr21, 9); p.t21 = _c_floats(t21, 3)
+        p.th = float(pr["th"])
+        o = dict(match12=np.full(max(n1, 1), -3, np.int32), match1=np.full(max(n1, 1), -3, np.int32), match2=np.full(max(n2, 1), -3, np.int32))
+        for name, v in o.items():
+            setattr(p, name, v.ctypes.data)
+        p.nfound = -2
+        outs.append((o, n1, n2))
+    f1 = [pr["kf1"].get("frame") for pr in problems]
+    f2 = [pr["kf2"].get("frame") for pr in problems]
+    if all(f is None for f in f1 + f2):
+        rc = lib.ps_search_by_sim3(self._h, arr, n)
+    else:
+        h = lambda fs: (ctypes.c_void_p * n)(*[None if f is None else f._h.value for f in fs])
+        rc = lib.ps_search_by_sim3_frames(self._h, arr, h(f1), h(f2), n)
+    if not (partial_ok and rc == -3):
+        check(rc)
+    return [dict(nfound=int(arr[i].nfound), match12=o["match12"][:n1].copy(), match1=o["match1"][:n1].copy(), match2=o["match2"][:n2].copy())
+            for i, (o, n1, n2) in enumerate(outs)]
+
+
+def _search_by_sim3(self, *args, **kw):
+    """SearchBySim3(problems) for a batch (see _search_by_sim3_batch), or the reference's own call for one pair:
+    SearchBySim3(kf1, kf2, matches12, s12, R12, t12, th) with keyframe dicts as in _fill_sim3_side (K4 on kf1, `already` is built here)
+    and matches12 int [n1] = the slot of keyframe 2 that holds vpMatches12[i] (GetIndexInKeyFrame), -1 for NULL, any other negative
+    value for a point keyframe 2 does not hold.  -> (nfound, matches12 with the new pairs filled in)"""
+    if len(args) == 1:
+        return _search_by_sim3_batch(self, args[0], **kw)
+    kf1, kf2, matches12, s12, R12, t12, th = args
+    m12 = np.asarray(matches12, np.int64)
+    n2 = len(kf2["has_point"])
+    a1 = (m12 != -1).astype(np.uint8)
+    a2 = np.zeros(n2, np.uint8)
+    a2[m12[(m12 >= 0) & (m12 < n2)]] = 1
+    r = _search_by_sim3_batch(self, [dict(kf1=dict(kf1, already=a1), kf2=dict(kf2, already=a2), K4=kf1["K4"], s12=s12, R12=R12, t12=t12, th=th)])[0]
+    out = m12.copy()
+    out[r["match12"] >= 0] = r["match12"][r["match12"] >= 0]
+    return r["nfound"], out.astype(np.int32)
+
+
+lib.ps_kf_search.argtypes = [ctypes.c_void_p, ctypes.POINTER(_KfSearchProblem), ctypes.c_int]
+lib.ps_kf_search_frames.argtypes = [ctypes.c_void_p, ctypes.POINTER(_KfSearchProblem), ctypes.POINTER(ctypes.c_void_p), ctypes.c_int]
+lib.ps_search_by_sim3.argtypes = [ctypes.c_void_p, ctypes.POINTER(_Sim3Problem), ctypes.c_int]
+lib.ps_search_by_sim3_frames.argtypes = [ctypes.c_void_p, ctypes.POINTER(_Sim3Problem), ctypes.POINTER(ctypes.c_void_p),
+                                         ctypes.POINTER(ctypes.c_void_p), ctypes.c_int]
+
+
+def _kf_search_tuples(self, problems, mode, partial_ok):
+    return [(r["nmatches"], r["match_of_train"]) for r in _kf_search(self, problems, partial_ok, mode)]
+
+
+ORBmatcher.KfSearch = _kf_search
+# SearchByProjection(pKF, Scw, vpPoints, vpMatched, th): [(nmatches, match_of_train)]
+ORBmatcher.SearchByProjectionSim3 = lambda self, problems, partial_ok=False: _kf_search_tuples(self, problems, 0, partial_ok)
+# Fuse(pKF, Scw, vpPoints, th, vpReplacePoint): [(best_idx, best_dist)]
+ORBmatcher.FuseSim3 = lambda self, problems, partial_ok=False: [(r["best_idx"], r["best_dist"]) for r in _kf_search(self, problems, partial_ok, 1)]
+# SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist): [(nmatches, match_of_train)]
+ORBmatcher.SearchByProjectionKeyFrame = lambda self, problems, partial_ok=False: _kf_search_tuples(self, problems, 2, partial_ok)
+ORBmatcher.SearchBySim3 = _search_by_sim3
