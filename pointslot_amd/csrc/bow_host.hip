@@ -26,10 +26,6 @@ struct ps_vocabulary {
   BowTree tree = {};
 };
 
-namespace {
-inline size_t al(size_t v) { return (v + 255) / 256 * 256; }
-}  // namespace
-
 extern "C" {
 
 int ps_vocabulary_create(int device, int k, int L, int scoring, int weighting, int nnodes, const int32_t* parent, const uint8_t* desc,
@@ -63,12 +59,11 @@ int ps_vocabulary_create(int device, int k, int L, int scoring, int weighting, i
     if (is_leaf[i]) { slot[s].off_or_word = nwords++; word_weight.push_back(weight[i]); }
   }
   PS_HIP(hipSetDevice(device));
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t r = off; off += al(bytes + 64); return r; };
-  const size_t o_slot = take(sizeof(BowSlot) * (size_t)nnodes), o_cd = take((size_t)nnodes * 32), o_ww = take((size_t)nwords * 4);
+  Arena a;
+  const size_t o_slot = a.take(sizeof(BowSlot) * (size_t)nnodes), o_cd = a.take((size_t)nnodes * 32), o_ww = a.take((size_t)nwords * 4);
   ps_vocabulary* v = new ps_vocabulary();
   v->device = device; v->k = k; v->L = L; v->weighting = weighting; v->nodes = (int)NN; v->words = nwords;
-  hipError_t e = hipMalloc(&v->d_slab, off);
+  hipError_t e = hipMalloc(&v->d_slab, a.off);
   if (e == hipSuccess) e = hipMemcpy(v->d_slab + o_slot, slot.data(), sizeof(BowSlot) * (size_t)nnodes, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(v->d_slab + o_cd, child_desc.data(), (size_t)nnodes * 32, hipMemcpyHostToDevice);
   if (e == hipSuccess && nwords > 0) e = hipMemcpy(v->d_slab + o_ww, word_weight.data(), (size_t)nwords * 4, hipMemcpyHostToDevice);
@@ -134,14 +129,12 @@ int ps_bow_transform(ps_matcher* m, const ps_vocabulary* v, ps_bow_problem* prob
     if (NF > 0x7FFFFFF0ull) return ps_set_error(PS_ERR_CAPACITY, "ps_bow_transform: the batch holds more than 2^31 features");
   }
   const size_t NB = NF / 16;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t r = off; off += al(bytes + 64); return r; };
-  const size_t o_frame = take(sizeof(BowFrame) * ns), o_ff = take(NB * 4), o_desc = take(NF * 32);
-  const size_t in_bytes = off;
-  const size_t o_word = take(NF * 4), o_node = take(NF * 4), o_id = take(NF * 4), o_n = take((size_t)ns * 4), o_val = take(NF * 8);
-  const size_t out_end = off;
-  int rc = psm_ensure(m, off);
-  if (rc != PS_OK) return rc;
+  Arena a;
+  const size_t o_frame = a.take(sizeof(BowFrame) * ns), o_ff = a.take(NB * 4), o_desc = a.take(NF * 32);
+  const size_t in_bytes = a.off;
+  const size_t o_word = a.take(NF * 4), o_node = a.take(NF * 4), o_id = a.take(NF * 4), o_n = a.take((size_t)ns * 4), o_val = a.take(NF * 8);
+  const size_t out_end = a.off;
+  PS_TRY(psm_ensure(m, a.off));
   uint8_t* H = m->h_buf;
   memcpy(H + o_frame, hf.data(), sizeof(BowFrame) * ns);
   ps_parallel_for(ns, in_bytes, [&](int s) {
@@ -152,18 +145,17 @@ int ps_bow_transform(ps_matcher* m, const ps_vocabulary* v, ps_bow_problem* prob
   });
   uint8_t* D = m->d_buf;
   PS_HIP(hipMemcpyAsync(D, H, in_bytes, hipMemcpyHostToDevice, m->stream));
-  hipEventRecord(m->ev0, m->stream);
+  PS_TRY(psm_kernels_begin(m));
   BowTransformArrays A;
   A.tree = v->tree;
   A.frame = (const BowFrame*)(D + o_frame); A.desc = D + o_desc; A.feat_frame = (const int32_t*)(D + o_ff);
   A.word = (int32_t*)(D + o_word); A.node = (int32_t*)(D + o_node); A.bow_id = (int32_t*)(D + o_id); A.bow_val = (double*)(D + o_val);
   A.bow_n = (int32_t*)(D + o_n); A.nblocks16 = (int32_t)NB;
   psk_bow_transform_launch(&A, ns, m->stream);
-  hipEventRecord(m->ev1, m->stream);
-  PS_HIP(hipGetLastError());
+  PS_TRY(psm_kernels_end(m));
   PS_HIP(hipMemcpyAsync(H + o_word, D + o_word, out_end - o_word, hipMemcpyDeviceToHost, m->stream));
   PS_HIP(hipStreamSynchronize(m->stream));
-  hipEventElapsedTime(&m->last_kernel_ms, m->ev0, m->ev1);
+  PS_TRY(psm_kernels_ms(m));
   ps_parallel_for(ns, out_end - o_word, [&](int s) {
     ps_bow_problem& P = probs[served[s]];
     const size_t f = (size_t)hf[s].f_off;
@@ -269,15 +261,13 @@ extern "C" int ps_search_by_bow(ps_matcher* m, ps_bow_search_problem* probs, int
     item_off[s] = NI; NI += plan[s].items.size();
     if (NF > 0x7FFFFFF0ull || NI > 0x7FFFFFF0ull) return ps_set_error(PS_ERR_CAPACITY, "ps_search_by_bow: the batch holds more than 2^31 features");
   }
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t r = off; off += al(bytes + 64); return r; };
-  const size_t o_prob = take(sizeof(BowSProb) * ns), o_item = take(sizeof(BowSItem) * NI), o_lst = take(NL * 4);
-  const size_t o_desc = take(NF * 32), o_ang = take(NF * 4), o_hasp = take(NF);
-  const size_t in_bytes = off;
-  const size_t o_match = take(NO * 4), o_nm = take((size_t)ns * 4);
-  const size_t out_end = off;
-  int rc = psm_ensure(m, off);
-  if (rc != PS_OK) return rc;
+  Arena a;
+  const size_t o_prob = a.take(sizeof(BowSProb) * ns), o_item = a.take(sizeof(BowSItem) * NI), o_lst = a.take(NL * 4);
+  const size_t o_desc = a.take(NF * 32), o_ang = a.take(NF * 4), o_hasp = a.take(NF);
+  const size_t in_bytes = a.off;
+  const size_t o_match = a.take(NO * 4), o_nm = a.take((size_t)ns * 4);
+  const size_t out_end = a.off;
+  PS_TRY(psm_ensure(m, a.off));
   uint8_t* H = m->h_buf;
   memcpy(H + o_prob, hp.data(), sizeof(BowSProb) * ns);
   ps_parallel_for(ns, in_bytes, [&](int s) {
@@ -302,17 +292,16 @@ extern "C" int ps_search_by_bow(ps_matcher* m, ps_bow_search_problem* probs, int
   uint8_t* D = m->d_buf;
   PS_HIP(hipMemcpyAsync(D, H, in_bytes, hipMemcpyHostToDevice, m->stream));
   if (NO > 0) PS_HIP(hipMemsetAsync(D + o_match, 0xFF, NO * 4, m->stream));   // -1 everywhere: vector<MapPoint*>(N, NULL)
-  hipEventRecord(m->ev0, m->stream);
+  PS_TRY(psm_kernels_begin(m));
   BowSearchArrays A;
   A.prob = (const BowSProb*)(D + o_prob); A.item = (const BowSItem*)(D + o_item);
   A.desc = D + o_desc; A.ang = (const float*)(D + o_ang); A.hasp = D + o_hasp; A.lst = (const int32_t*)(D + o_lst);
   A.match = (int32_t*)(D + o_match); A.nmatch = (int32_t*)(D + o_nm); A.nitems = (int32_t)NI; A.nprob = ns;
   psk_bow_search_launch(&A, m->stream);
-  hipEventRecord(m->ev1, m->stream);
-  PS_HIP(hipGetLastError());
+  PS_TRY(psm_kernels_end(m));
   PS_HIP(hipMemcpyAsync(H + o_match, D + o_match, out_end - o_match, hipMemcpyDeviceToHost, m->stream));
   PS_HIP(hipStreamSynchronize(m->stream));
-  hipEventElapsedTime(&m->last_kernel_ms, m->ev0, m->ev1);
+  PS_TRY(psm_kernels_ms(m));
   for (int s = 0; s < ns; s++) {
     ps_bow_search_problem& P = probs[served[s]];
     P.nmatches = ((const int32_t*)(H + o_nm))[s];

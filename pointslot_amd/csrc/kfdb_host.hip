@@ -33,7 +33,6 @@ struct ps_kfdb {
 };
 
 namespace {
-inline size_t al(size_t v) { return (v + 255) / 256 * 256; }
 bool ascending(const int32_t* id, int n) {
   for (int i = 0; i < n; i++)
     if (id[i] < 0 || (i > 0 && id[i] <= id[i - 1])) return false;
@@ -130,18 +129,17 @@ int ps_kfdb_add(ps_kfdb* db, ps_matcher* m, const int64_t* ids, const int32_t* c
   auto undo = [&]() { for (int i = 0; i < ns; i++) db->free_slots.insert(slot[i]); };
   if (ns > 0) {
     std::lock_guard<std::mutex> lock(m->mu);
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t r = o; o += al(bytes + 64); return r; };
-    const size_t o_slot = take((size_t)ns * 4), o_off = take((size_t)ns * 4), o_n = take((size_t)ns * 4), o_ser = take((size_t)ns * 4), o_kfid = take((size_t)ns * 8);
-    const size_t o_id = take(NW * 4), o_val = take(NW * 8);
+    Arena a;
+    const size_t o_slot = a.take((size_t)ns * 4), o_off = a.take((size_t)ns * 4), o_n = a.take((size_t)ns * 4), o_ser = a.take((size_t)ns * 4), o_kfid = a.take((size_t)ns * 8);
+    const size_t o_id = a.take(NW * 4), o_val = a.take(NW * 8);
     hipError_t he = hipSetDevice(m->device);
-    int rc = he == hipSuccess ? psm_ensure(m, o) : ps_set_error(PS_ERR_HIP, "ps_kfdb_add: %s", hipGetErrorString(he));
+    int rc = he == hipSuccess ? psm_ensure(m, a.off) : ps_set_error(PS_ERR_HIP, "ps_kfdb_add: %s", hipGetErrorString(he));
     if (rc != PS_OK) { undo(); return rc; }
     uint8_t* H = m->h_buf;
     memcpy(H + o_slot, slot.data(), (size_t)ns * 4); memcpy(H + o_off, off.data(), (size_t)ns * 4); memcpy(H + o_n, len.data(), (size_t)ns * 4);
     memcpy(H + o_ser, serial.data(), (size_t)ns * 4);
     for (int i = 0; i < ns; i++) ((int64_t*)(H + o_kfid))[i] = ids[src[i]];
-    ps_parallel_for(ns, o, [&](int i) {
+    ps_parallel_for(ns, a.off, [&](int i) {
       if (len[i] == 0) return;
       memcpy(H + o_id + (size_t)off[i] * 4, bow_id[src[i]], (size_t)len[i] * 4);
       memcpy(H + o_val + (size_t)off[i] * 8, bow_val[src[i]], (size_t)len[i] * 8);
@@ -152,7 +150,7 @@ int ps_kfdb_add(ps_kfdb* db, ps_matcher* m, const int64_t* ids, const int32_t* c
     A.slot = (const int32_t*)(D + o_slot); A.off = (const int32_t*)(D + o_off); A.n = (const int32_t*)(D + o_n);
     A.serial = (const uint32_t*)(D + o_ser); A.kfid = (const int64_t*)(D + o_kfid);
     A.src_id = (const int32_t*)(D + o_id); A.src_val = (const double*)(D + o_val);
-    he = hipMemcpyAsync(D, H, o, hipMemcpyHostToDevice, m->stream);
+    he = hipMemcpyAsync(D, H, a.off, hipMemcpyHostToDevice, m->stream);
     if (he == hipSuccess) { psk_kfdb_put_launch(&A, ns, m->stream); he = hipGetLastError(); }
     if (he == hipSuccess) he = hipStreamSynchronize(m->stream);
     if (he != hipSuccess) { undo(); return ps_set_error(PS_ERR_HIP, "ps_kfdb_add: %s", hipGetErrorString(he)); }
@@ -250,17 +248,15 @@ int ps_kfdb_query(ps_kfdb* db, ps_matcher* m, ps_kfdb_query_problem* probs, int 
   }
   for (int s = 0; s < ns; s++) if (hq[s].mode == 0) order.push_back(s);
   const size_t Q = (size_t)ns, QH = Q * (size_t)high, QL = Q * (size_t)live;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t r = off; off += al(bytes + 64); return r; };
-  const size_t o_q = take(sizeof(KfdbQuery) * Q), o_order = take(Q * 4), o_excl = take(excl.size() * 4), o_qid = take(NW * 4), o_qval = take(NW * 8);
-  const size_t in_bytes = off;
-  const size_t o_maxw = take(Q * 4), o_words = take(QH * 4), o_lcw = take(QH * 4), o_score = take(QH * 4);
-  const size_t o_sid = take(QL * 8), o_sw = take(QL * 4), o_ss = take(QL * 4), o_ns = take(Q * 4), o_mc = take(Q * 4);
-  const size_t out_end = off;
+  Arena a;
+  const size_t o_q = a.take(sizeof(KfdbQuery) * Q), o_order = a.take(Q * 4), o_excl = a.take(excl.size() * 4), o_qid = a.take(NW * 4), o_qval = a.take(NW * 8);
+  const size_t in_bytes = a.off;
+  const size_t o_maxw = a.take(Q * 4), o_words = a.take(QH * 4), o_lcw = a.take(QH * 4), o_score = a.take(QH * 4);
+  const size_t o_sid = a.take(QL * 8), o_sw = a.take(QL * 4), o_ss = a.take(QL * 4), o_ns = a.take(Q * 4), o_mc = a.take(Q * 4);
+  const size_t out_end = a.off;
   std::lock_guard<std::mutex> lock(m->mu);
   PS_HIP(hipSetDevice(m->device));
-  int rc = psm_ensure(m, off);
-  if (rc != PS_OK) return rc;
+  PS_TRY(psm_ensure(m, a.off));
   uint8_t* H = m->h_buf;
   memcpy(H + o_q, hq.data(), sizeof(KfdbQuery) * Q);
   memcpy(H + o_order, order.data(), Q * 4);
@@ -274,7 +270,7 @@ int ps_kfdb_query(ps_kfdb* db, ps_matcher* m, ps_kfdb_query_problem* probs, int 
   uint8_t* D = m->d_buf;
   PS_HIP(hipMemcpyAsync(D, H, in_bytes, hipMemcpyHostToDevice, m->stream));
   PS_HIP(hipMemsetAsync(D + o_maxw, 0, Q * 4, m->stream));
-  hipEventRecord(m->ev0, m->stream);
+  PS_TRY(psm_kernels_begin(m));
   KfdbQueryArrays A;
   A.S = db->S;
   A.q = (const KfdbQuery*)(D + o_q); A.qid = (const int32_t*)(D + o_qid); A.qval = (const double*)(D + o_qval);
@@ -285,11 +281,10 @@ int ps_kfdb_query(ps_kfdb* db, ps_matcher* m, ps_kfdb_query_problem* probs, int 
   A.share_id = (int64_t*)(D + o_sid); A.share_words = (int32_t*)(D + o_sw); A.share_score = (float*)(D + o_ss);
   A.nshare = (int32_t*)(D + o_ns); A.mincw = (int32_t*)(D + o_mc);
   psk_kfdb_query_launch(&A, longest, m->stream);
-  hipEventRecord(m->ev1, m->stream);
-  PS_HIP(hipGetLastError());
+  PS_TRY(psm_kernels_end(m));
   PS_HIP(hipMemcpyAsync(H + o_sid, D + o_sid, out_end - o_sid, hipMemcpyDeviceToHost, m->stream));
   PS_HIP(hipStreamSynchronize(m->stream));
-  hipEventElapsedTime(&m->last_kernel_ms, m->ev0, m->ev1);
+  PS_TRY(psm_kernels_ms(m));
   for (int s = 0; s < ns; s++) {
     ps_kfdb_query_problem& P = probs[served[s]];
     const size_t k = (size_t)s * (size_t)live;
@@ -317,31 +312,28 @@ int ps_kfdb_score(ps_kfdb* db, ps_matcher* m, const int32_t* bow_id, const doubl
     slot[(size_t)i] = it == db->slot_of.end() ? -1 : it->second;
     unknown += it == db->slot_of.end();
   }
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t r = off; off += al(bytes + 64); return r; };
-  const size_t o_slot = take((size_t)n * 4), o_qid = take((size_t)bow_n * 4), o_qval = take((size_t)bow_n * 8);
-  const size_t in_bytes = off;
-  const size_t o_out = take((size_t)n * 8);
+  Arena a;
+  const size_t o_slot = a.take((size_t)n * 4), o_qid = a.take((size_t)bow_n * 4), o_qval = a.take((size_t)bow_n * 8);
+  const size_t in_bytes = a.off;
+  const size_t o_out = a.take((size_t)n * 8);
   std::lock_guard<std::mutex> lock(m->mu);
   PS_HIP(hipSetDevice(m->device));
-  int rc = psm_ensure(m, off);
-  if (rc != PS_OK) return rc;
+  PS_TRY(psm_ensure(m, a.off));
   uint8_t* H = m->h_buf;
   memcpy(H + o_slot, slot.data(), (size_t)n * 4);
   if (bow_n > 0) { memcpy(H + o_qid, bow_id, (size_t)bow_n * 4); memcpy(H + o_qval, bow_val, (size_t)bow_n * 8); }
   uint8_t* D = m->d_buf;
   PS_HIP(hipMemcpyAsync(D, H, in_bytes, hipMemcpyHostToDevice, m->stream));
-  hipEventRecord(m->ev0, m->stream);
+  PS_TRY(psm_kernels_begin(m));
   KfdbScoreArrays A;
   A.S = db->S;
   A.qid = (const int32_t*)(D + o_qid); A.qval = (const double*)(D + o_qval); A.qn = bow_n;
   A.slot = (const int32_t*)(D + o_slot); A.n = n; A.out = (double*)(D + o_out);
   psk_kfdb_score_launch(&A, m->stream);
-  hipEventRecord(m->ev1, m->stream);
-  PS_HIP(hipGetLastError());
+  PS_TRY(psm_kernels_end(m));
   PS_HIP(hipMemcpyAsync(H + o_out, D + o_out, (size_t)n * 8, hipMemcpyDeviceToHost, m->stream));
   PS_HIP(hipStreamSynchronize(m->stream));
-  hipEventElapsedTime(&m->last_kernel_ms, m->ev0, m->ev1);
+  PS_TRY(psm_kernels_ms(m));
   memcpy(out, H + o_out, (size_t)n * 8);
   if (unknown > 0) return ps_set_error(PS_ERR_INVALID, "ps_kfdb_score: %d of the ids are not stored", unknown);
   return PS_OK;

@@ -17,6 +17,13 @@ int ps_set_error(int code, const char* fmt, ...) __attribute__((format(printf, 2
       return ps_set_error(PS_ERR_HIP, "%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(_e)); \
   } while (0)
 
+// returns a library call's code to the caller unless it is PS_OK
+#define PS_TRY(expr)                  \
+  do {                                \
+    const int _rc = (expr);           \
+    if (_rc != PS_OK) return _rc;     \
+  } while (0)
+
 // Host-side staging helper: fn(i) for i in [0, n), spread over short-lived threads when the job moves enough bytes to pay
 // for them (packing a batch of problems into the pinned upload buffer is a memcpy-bound loop over independent slices).
 template <typename Fn>

@@ -145,19 +145,6 @@ def _arr(a, dt):
     return np.ascontiguousarray(a, dt)
 
 
-def _fill_train_from_frame(p, F, keep):
-    """the train side lives in a DeviceFrame (F["frame"]): only what changes from call to call comes from the host"""
-    n = len(F["frame"])
-    a = dict(occupied=_arr(F.get("occupied", np.zeros(n, np.uint8)), np.uint8), in_bbox=_arr(F.get("in_bbox", np.ones(n, np.uint8)), np.uint8))
-    if len(a["occupied"]) != n or len(a["in_bbox"]) != n:
-        raise ValueError("occupied / in_bbox must have one entry per keypoint of the frame (%d)" % n)
-    keep.append(a)
-    p.train.n = n
-    for k, v in a.items():
-        setattr(p.train, k, v.ctypes.data)
-    return n
-
-
 def _frame_handles(problems):
     """(ctypes array of ps_frame* or None per problem) when any problem of the batch is frame-backed, else None"""
     fr = [pr["train"].get("frame") for pr in problems]
@@ -166,21 +153,30 @@ def _frame_handles(problems):
     return (ctypes.c_void_p * len(fr))(*[None if f is None else f._h.value for f in fr])
 
 
-def _fill_train(p, F, keep):
-    if F.get("frame") is not None:
-        return _fill_train_from_frame(p, F, keep)
-    n = len(F["x"])
-    a = dict(x=_arr(F["x"], np.float32), y=_arr(F["y"], np.float32), octave=_arr(F["octave"], np.int32),
-             angle=_arr(F["angle"], np.float32), u_right=_arr(F["u_right"], np.float32),
-             desc=_arr(F["desc"], np.uint8).reshape(-1, 32), occupied=_arr(F["occupied"], np.uint8),
-             in_bbox=_arr(F.get("in_bbox", np.ones(n, np.uint8)), np.uint8),
-             cell_off=_arr(F["cell_off"], np.int32), cell_idx=_arr(F["cell_idx"], np.int32))
-    keep.append(a)
-    t = p.train
-    t.n = n
+def _fill_train(t, F, keep, *, need=("angle", "u_right", "occupied", "in_bbox")):
+    """One ps_proj_train from a searched-side dict: x, y, octave, desc, cell_off, cell_idx, grid and, of angle, u_right, occupied and
+    in_bbox, those the call reads (`need`; angle and occupied default to zeros, in_bbox to ones) - or "frame" = a DeviceFrame that
+    holds the keypoints and the grid, beside which only occupied and in_bbox stay host arrays.  Returns the number of keypoints."""
+    frame = F.get("frame")
+    if frame is None:
+        n = len(F["x"])
+        a = dict(x=_arr(F["x"], np.float32), y=_arr(F["y"], np.float32), octave=_arr(F["octave"], np.int32),
+                 desc=_arr(F["desc"], np.uint8).reshape(-1, 32), cell_off=_arr(F["cell_off"], np.int32), cell_idx=_arr(F["cell_idx"], np.int32))
+        t.min_x, t.min_y, t.grid_w_inv, t.grid_h_inv = [float(v) for v in F["grid"]]
+    else:
+        n, a = len(frame), {}
+    for k in need:
+        if k == "u_right" or k == "angle":                  # in the frame's slab, when there is one
+            if frame is None:
+                a[k] = np.zeros(n, np.float32) if k == "angle" and k not in F else _arr(F[k], np.float32)
+        else:
+            a[k] = _arr(F[k], np.uint8) if k in F else np.full(n, k == "in_bbox", np.uint8)
     for k, v in a.items():
+        if len(v) != n and k != "cell_off" and k != "cell_idx":
+            raise ValueError("the arrays of a searched side differ in length: %s has %d entries, the side %d keypoints" % (k, len(v), n))
         setattr(t, k, v.ctypes.data)
-    t.min_x, t.min_y, t.grid_w_inv, t.grid_h_inv = [float(v) for v in F["grid"]]
+    keep.append(a)
+    t.n = n
     return n
 
 
@@ -214,7 +210,7 @@ def _search_by_projection(self, problems, partial_ok=False):
 
 def _fill_projection_problem(self, p, pr, keep, outs):
     """one ps_proj_problem from its dict (see _search_by_projection)"""
-    nt = _fill_train(p, pr["train"], keep)
+    nt = _fill_train(p.train, pr["train"], keep)
     q = pr["query"]
     nq = len(q["valid"])
     a = dict(q_valid=_arr(q["valid"], np.uint8), q_desc=_arr(q["desc"], np.uint8).reshape(-1, 32),
@@ -279,11 +275,7 @@ def _fuse_search(self, problems):
     keep, outs = [], []
     for i, pr in enumerate(problems):
         p = arr[i]
-        F = dict(pr["train"])
-        if F.get("frame") is None:
-            nt = len(F["x"])
-            F.setdefault("angle", np.zeros(nt, np.float32)); F.setdefault("occupied", np.zeros(nt, np.uint8))
-        _fill_train(p, F, keep)
+        _fill_train(p.train, pr["train"], keep, need=("u_right",))
         q = pr["query"]
         m = len(q["valid"])
         a = dict(q_valid=_arr(q["valid"], np.uint8), q_pos=_arr(q["pos"], np.float32).reshape(-1, 3), q_normal=_arr(q["normal"], np.float32).reshape(-1, 3),
@@ -553,34 +545,12 @@ class _Sim3Problem(ctypes.Structure):
                 ("nfound", ctypes.c_int32)]
 
 
-def _fill_kf_train(t, F, keep, need_occupied):
-    """the searched side of a ps_kf_search / ps_search_by_sim3 problem: x, y, octave, desc, cell_off, cell_idx, grid (angle, occupied
-    where the mode reads them), or "frame" = a DeviceFrame holding them (occupied stays a host array)"""
-    framed = F.get("frame") is not None
-    n = len(F["frame"]) if framed else len(F["x"])
-    a = {}
-    if not framed:
-        a.update(x=_arr(F["x"], np.float32), y=_arr(F["y"], np.float32), octave=_arr(F["octave"], np.int32),
-                 angle=_arr(F.get("angle", np.zeros(n, np.float32)), np.float32), desc=_arr(F["desc"], np.uint8).reshape(-1, 32),
-                 cell_off=_arr(F["cell_off"], np.int32), cell_idx=_arr(F["cell_idx"], np.int32))
-        t.min_x, t.min_y, t.grid_w_inv, t.grid_h_inv = [float(v) for v in F["grid"]]
-    if need_occupied:
-        a["occupied"] = _arr(F.get("occupied", np.zeros(n, np.uint8)), np.uint8)
-    if any(len(v) != n for k, v in a.items() if k not in ("cell_off", "cell_idx")):
-        raise ValueError("the arrays of a searched side differ in length")
-    keep.append(a)
-    t.n = n
-    for k, v in a.items():
-        setattr(t, k, v.ctypes.data)
-    return n
-
-
 def _c_floats(v, n):
     return (ctypes.c_float * n)(*np.asarray(v, np.float32).reshape(n))
 
 
 def _kf_search(self, problems, partial_ok=False, mode=None):
-    """ps_kf_search for a batch.  problems: list of dicts {mode 0 / 1 / 2 (or the `mode` argument for all), train (see _fill_kf_train),
+    """ps_kf_search for a batch.  problems: list of dicts {mode 0 / 1 / 2 (or the `mode` argument for all), train (see _fill_train),
     query {valid, pos [m, 3], normal [m, 3] (modes 0, 1), min_dist, max_dist, desc [m, 32], angle (mode 2)}, R, t, ow (decompose_scw
     for the Sim3 overloads; GetRotation / GetTranslation / GetCameraCenter of the frame in mode 2), K4 (fx, fy, cx, cy), bounds,
     scale_factors, log_scale_factor, n_levels, th, th_dist (mode 2: ORBdist), check_orientation (mode 2; default: the matcher's)}.
@@ -594,7 +564,7 @@ def _kf_search(self, problems, partial_ok=False, mode=None):
     for i, pr in enumerate(problems):
         p = arr[i]
         p.mode = int(pr["mode"] if mode is None else mode)
-        nt = _fill_kf_train(p.train, pr["train"], keep, p.mode != 1)
+        nt = _fill_train(p.train, pr["train"], keep, need=("angle", "occupied") if p.mode != 1 else ("angle",))
         q = pr["query"]
         m = len(q["valid"])
         a = dict(q_valid=_arr(q["valid"], np.uint8), q_pos=_arr(q["pos"], np.float32).reshape(-1, 3), q_min_dist=_arr(q["min_dist"], np.float32),
@@ -638,9 +608,9 @@ def _kf_search(self, problems, partial_ok=False, mode=None):
 
 
 def _fill_sim3_side(c, kf, keep):
-    """one ps_sim3_side from a keyframe dict: the searched-side keys of _fill_kf_train plus has_point, pos [n, 3], min_dist, max_dist,
+    """one ps_sim3_side from a keyframe dict: the searched-side keys of _fill_train plus has_point, pos [n, 3], min_dist, max_dist,
     point_desc [n, 32], already, R, t, bounds, scale_factors, log_scale_factor, n_levels"""
-    n = _fill_kf_train(c.train, kf, keep, False)
+    n = _fill_train(c.train, kf, keep, need=("angle",))
     a = dict(has_point=_arr(kf["has_point"], np.uint8), pos=_arr(kf["pos"], np.float32).reshape(-1, 3), min_dist=_arr(kf["min_dist"], np.float32),
              max_dist=_arr(kf["max_dist"], np.float32), point_desc=_arr(kf["point_desc"], np.uint8).reshape(-1, 32),
              already=_arr(kf.get("already", np.zeros(n, np.uint8)), np.uint8))

@@ -127,7 +127,8 @@ def _angle_pair(rng, spread):
     return F32((ta + rot) % 360.0), F32(ta)
 
 
-def _main(mode, seed, nf=500, nq=500, th=10.0, spread=False, **kw):
+def _main(mode, seed, nf=500, nq=500, th=10.0, spread=False, first=0, **kw):
+    """first: where in the cycle of 29 point kinds the case starts (7: behind the special ones, so a short case has plain points)"""
     rng = np.random.RandomState(seed)
     sc = _Scene(rng, mode, _pose_for(rng, mode))
     n_seen = min(nf, nq) * 7 // 10
@@ -142,7 +143,7 @@ def _main(mode, seed, nf=500, nq=500, th=10.0, spread=False, **kw):
             sc.feature(u + rng.uniform(-1.5, 1.5), v + rng.uniform(-1.5, 1.5), octave, desc, angle=ta, occupied=int(rng.rand() < 0.1))
         # the predicted level against the feature's octave: inside the member's window, at its edges, and one step outside
         level = int(np.clip(octave + rng.choice([0, 0, 1, 1, -1, 2]), 0, 7))
-        kind = special[i % 29] if i % 29 < len(special) else "plain"
+        kind = special[(i + first) % 29] if (i + first) % 29 < len(special) else "plain"
         pd = _flip(rng, desc, int(rng.randint(0, 61)))
         if kind == "invalid":
             sc.point(xc, pd, level, valid=0, angle=qa)
@@ -272,8 +273,8 @@ def _over():
     return [_main(0, 80, nf=120, nq=90), big, _main(2, 82, nf=120, nq=90)]
 
 
-def _empty(mode, which):
-    pr = _main(mode, 90 + mode, nf=60, nq=40)
+def _empty(mode, which, **kw):
+    pr = _main(mode, 90 + mode, nf=60, nq=40) if not kw else _main(mode, **kw)
     if which == "nq":
         pr["query"] = {k: v[:0] for k, v in pr["query"].items()}
     else:
@@ -390,6 +391,10 @@ KF_BUILDERS = {
 KF_BUILDERS.update({"batch_%02d" % k: (lambda k=k: _main(k % 3, 100 + k, nf=90 + 17 * k, nq=70 + 13 * k, th=(10.0, 4.0, 10.0)[k % 3]))
                     for k in range(16)})
 BATCH = tuple("batch_%02d" % k for k in range(16))
+# one call, three problems, one of each mode: 65 features (one more than a wave) and 5 points each, the third searched side empty
+KF_BUILDERS.update({"mixed_0": lambda: _main(0, 130, nf=65, nq=5, first=7), "mixed_1": lambda: _main(1, 131, nf=65, nq=5, th=4.0, first=7),
+                    "mixed_2": lambda: _empty(2, "n", seed=132, nf=65, nq=5, first=7)})
+MIXED = ("mixed_0", "mixed_1", "mixed_2")
 SIM3_BUILDERS = {
     "sim3_main": lambda: _sim3_main(21, 1.0), "sim3_main_093": lambda: _sim3_main(22, 0.93),
     "sim3_tie": lambda: _sim3(23, 1.0, n=200, tie=True),

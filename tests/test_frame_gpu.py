@@ -316,6 +316,34 @@ def test_fuse_search_through_a_frame(matcher, handle, seed, kw):
     assert (gi >= 0).sum() > 50
 
 
+@gpu
+def test_fuse_search_mixed_batch(matcher, handle):
+    """One call with a frame-backed problem, a host-backed one and a frame-backed one whose frame is empty: some searched sides
+    are staged on the device, so nothing of the upload may be left out.  65 features (one more than a wave) and 5 candidate points
+    per problem; every array equals the one the same problem gives alone, from host arrays."""
+    from pointslot_amd import synth
+    from pointslot_amd.frame import DeviceFrame
+    from pointslot_amd.matcher import build_grid
+    a, b, c = (synth.fuse_scene(seed, n=65, m=5) for seed in (0x51070030, 0x51070031, 0x51070032))
+    for pr in (a, b):
+        T = pr["train"]
+        T["cell_off"], T["cell_idx"] = build_grid(T["x"], T["y"], *T["grid"])
+        _assert_input_condition(T["x"], T["y"], T["grid"])
+    z = np.zeros(0, np.float32)
+    c["train"] = {"x": z, "y": z, "octave": np.zeros(0, np.int32), "u_right": z, "desc": np.zeros((0, 32), np.uint8), "grid": c["train"]["grid"],
+                  "cell_off": np.zeros(64 * 48 + 1, np.int32), "cell_idx": np.zeros(0, np.int32)}
+    alone = [matcher.FuseSearch([pr])[0] for pr in (a, b, c)]
+    Ta = a["train"]
+    handle.publish(dict(Ta, angle=np.zeros(65, np.float32)), Ta["u_right"], Ta["desc"], Ta["grid"])
+    E = DeviceFrame(64)
+    E.publish({"x": z, "y": z, "octave": z, "angle": z}, z, np.zeros((0, 32), np.uint8), c["train"]["grid"])
+    mixed = matcher.FuseSearch([dict(a, train={"frame": handle}), b, dict(c, train={"frame": E})])
+    E.close()
+    for (gi, gd), (hi, hd) in zip(mixed, alone):
+        assert len(gi) == 5 and np.array_equal(gi, hi) and np.array_equal(gd, hd)
+    assert (alone[0][0] >= 0).any() and (alone[1][0] >= 0).any() and not (alone[2][0] >= 0).any()
+
+
 # ---- 6. errors -----------------------------------------------------------------------------------------------------------------------
 @gpu
 def test_frame_errors(matcher):

@@ -184,3 +184,17 @@ def test_cpp_and_python_state_the_same_decomposition_model(tmp_path):
     Rcw, tcw, ow, _ = decompose_scw(S)
     want = np.concatenate([np.asarray(v, F32).ravel() for v in (Rcw, tcw, ow) + tuple(sim3_pair(s12, R12, t12))]).view(np.uint32)
     assert np.array_equal(got, want), (got, want)
+
+
+def test_searched_side_packing_under_the_host_sanitizers(tmp_path):
+    """tests/cpp/search_side_check.cpp over pointslot_amd/csrc/search_side.h (a stand-alone program; nothing loaded into Python is
+    sanitized): the arena stride, the projection / fuse / kf_search layouts with skip ranges that are exactly the staged slots, and
+    side_pack on sides of 3, 0 and 2 features - the last with a grid that claims 5 entries over a cell_idx of exactly 2 - byte for
+    byte against values written out by hand, nothing touched outside the slices, no report from either sanitizer."""
+    exe = str(tmp_path / "search_side_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-I", os.path.join(ROOT, "pointslot_amd", "csrc"), os.path.join(ROOT, "tests", "cpp", "search_side_check.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
+    assert "ERROR: AddressSanitizer" not in out.stderr and "runtime error" not in out.stderr, out.stderr[-3000:]
+    assert out.stdout.strip().splitlines()[-1].startswith("ok ") and "FAILED" not in out.stdout, out.stdout

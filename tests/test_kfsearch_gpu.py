@@ -181,6 +181,24 @@ def test_searched_side_from_a_frame_handle(matcher):
     frame.close(); f1.close()
 
 
+def test_kf_search_mixed_batch(matcher):
+    """One call with a frame-backed problem (mode 0), a host-backed one (mode 1) and a frame-backed one whose frame is empty (mode 2):
+    some searched sides are staged on the device, so nothing of the upload may be left out.  65 features and 5 points each."""
+    probs = [kc.problem(n) for n in kc.MIXED]
+    assert [p["mode"] for p in probs] == [0, 1, 2] and [len(p["train"]["x"]) for p in probs] == [65, 65, 0]
+    assert all(len(p["query"]["valid"]) == 5 for p in probs) and kc.reference("mixed_0")["nmatches"] > 0 and kc.reference("mixed_1")["nmatches"] > 0
+    alone = [matcher.KfSearch([p])[0] for p in probs]
+    frames = [_published(probs[0]["train"]), None, _published(probs[2]["train"])]
+    via = [p if f is None else dict(p, train=dict(frame=f, occupied=p["train"]["occupied"])) for p, f in zip(probs, frames)]
+    got = matcher.KfSearch(via)
+    for name, p, g, a in zip(kc.MIXED, probs, got, alone):
+        _check_kf(g, kc.reference(name), p["mode"], name)
+        _check_kf(a, kc.reference(name), p["mode"], name + " alone")
+        for key in KF_KEYS[p["mode"]]:
+            assert np.array_equal(g[key], a[key]), (name, key)
+    frames[0].close(); frames[2].close()
+
+
 @pytest.mark.parametrize("name", sorted(kc.SIM3_BUILDERS))
 def test_search_by_sim3_equals_the_second_opinion(matcher, name):
     _check_sim3(matcher.SearchBySim3([kc.problem(name)])[0], kc.reference(name), name)
