@@ -71,6 +71,10 @@ int ps_kfdb_create(int device, int capacity, int max_words, ps_kfdb** out) {
   db->device = device; db->capacity = capacity; db->max_words = max_words;
   hipError_t e = hipMalloc(&db->d_slab, off);
   if (e == hipSuccess) e = hipMemset(db->d_slab + o_kfid, 0, off - o_kfid);
+  if (const char* fill = getenv("PS_DEBUG_FILL")) {   // diagnostic, as in psm_ensure: poison the rows (vals, ids), which nothing zeroes, and wait for the fill
+    if (e == hipSuccess) e = hipMemset(db->d_slab, atoi(fill), o_kfid);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+  }
   if (e != hipSuccess) {
     if (db->d_slab) hipFree(db->d_slab);
     delete db;

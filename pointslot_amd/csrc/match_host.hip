@@ -41,6 +41,10 @@ int psm_ensure_wide(ps_matcher* m, size_t bytes) {
   if (m->d_wide) hipFree(m->d_wide);
   m->d_wide = nullptr; m->d_wide_bytes = 0;
   PS_HIP(hipMalloc(&m->d_wide, bytes));
+  if (const char* fill = getenv("PS_DEBUG_FILL")) {   // diagnostic, as in psm_ensure: the fill has landed before the handle's stream uses the buffer
+    PS_HIP(hipMemset(m->d_wide, atoi(fill), bytes));
+    PS_HIP(hipDeviceSynchronize());
+  }
   m->d_wide_bytes = bytes;
   return PS_OK;
 }

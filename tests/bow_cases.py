@@ -136,6 +136,8 @@ TRANSFORM_CASES = {
     "full_k10_L3": dict(vocab=dict(seed=21, k=10, L=3), n=300, levelsup=(1,)),
     "pruned_k3_L6": dict(vocab=dict(seed=22, k=3, L=6, p_prune=0.25, p_stop=0.15, tie_siblings=0.3), n=200, levelsup=(0, 4, 9)),
     "wide_k20_L2": dict(vocab=dict(seed=23, k=20, L=2, p_stop=0.05), n=150, levelsup=(0, 1)),
+    # 10^4 words and a frame at the documented limit of 8191 features: thousands of distinct words, 32 sorted keys per thread of bow_vector
+    "limit_k10_L4": dict(vocab=dict(seed=24, k=10, L=4), n=8191, levelsup=(2,)),
 }
 
 

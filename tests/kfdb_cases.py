@@ -1,6 +1,6 @@
 """Cases for the keyframe database tests.  A case is a script: kfs = {id: BowVector}, neigh = {id: ordered ids of
-GetBestCovisibilityKeyFrames(10)} (ids that are never stored included), and ops - ("add", ids), ("erase", ids), ("clear",) or
-("query", [queries]) for one call serving several queries.  A query is a dict: qid, bow, mode (0 relocalisation, 1 loop),
+GetBestCovisibilityKeyFrames(10)} (ids that are never stored included), and ops - ("add", ids), ("erase", ids), ("clear",),
+("score", bow, ids) for ps_kfdb_score or ("query", [queries]) for one call serving several queries.  A query is a dict: qid, bow, mode (0 relocalisation, 1 loop),
 connected (the ids of GetConnectedKeyFrames()) and min_score.  second_opinion() plays a case through tests/kfdb_second_opinion.py
 once and is shared by all tests.  The sizes are small: seconds on the GPU; the workload's 1500-word vectors are for
 tools/kfdb_quick.py."""
@@ -192,14 +192,37 @@ def case_batch(split=False):
                 ops=[("add", stored)] + ([("query", [q]) for q in qs] if split else [("query", qs)]))
 
 
-CASES = {"hand": hand_case, "a": case_a, "b": case_b, "batch": case_batch, "batch_split": functools.partial(case_batch, True)}
+@functools.lru_cache(maxsize=None)
+def case_limit():
+    """one stored vector and one query of 8191 words (MAX_WORDS), beside shorter ones: 128 chunks of the wave sum's 64-word prefetch,
+    the whole 32 KB query in LDS, 13-step binary searches; query in both modes and ps_kfdb_score"""
+    rng = synth.Rng(4200)
+    nwords = 12000
+
+    def vec(n):
+        ids = np.sort(_sample(rng, np.arange(nwords), n)).astype(I32)
+        val = rng.uniform(n, 0.05, 1.0)
+        return ids, val / val.sum()
+    kfs = {1: vec(8191), 2: vec(300), 3: vec(8000), 4: vec(65), 5: vec(6000)}
+    q = vec(8191)
+    queries = [dict(qid=1, bow=q, mode=0, connected=[], min_score=0.0), dict(qid=2, bow=q, mode=1, connected=[3], min_score=0.0)]
+    return dict(nwords=nwords, capacity=5, max_words=8191, kfs=kfs, neigh={1: [3, 5], 3: [1], 5: [2, 1]},
+                ops=[("add", [1, 2, 3, 4, 5]), ("query", queries), ("score", q, [1, 2, 3, 4, 5])])
+
+
+CASES = {"limit": case_limit, "hand": hand_case, "a": case_a, "b": case_b, "batch": case_batch, "batch_split": functools.partial(case_batch, True)}
 
 
 @functools.lru_cache(maxsize=None)
 def second_opinion(name):
     """one result per query, in the order the case asks them: share_id, share_words, share_score, min_common_words, candidates,
     the query itself and the second opinion's trace"""
-    case = CASES[name]()
+    return play_second_opinion(CASES[name]())
+
+
+def play_second_opinion(case):
+    """The ops interpreter: a case script played through tests/kfdb_second_opinion.py.  One result per query, in order; an op
+    ("score", bow, ids) - ps_kfdb_score against stored keyframes - gives dict(scores=float64 array) in its place in that order."""
     db = so.KeyFrameDatabase(case["nwords"])
     obj = {}                                           # every keyframe of the map; an erased one that is added again is a new object
 
@@ -221,6 +244,8 @@ def second_opinion(name):
         elif op[0] == "clear":
             db.clear()
             stored.clear()
+        elif op[0] == "score":
+            out.append(dict(scores=np.array([so.score(list(zip(*op[1])), list(zip(*case["kfs"][i]))) for i in op[2]], np.float64)))
         else:
             for k in list(obj.values()):
                 k.neigh = [get(x) for x in case["neigh"].get(k.mnId, [])]

@@ -267,6 +267,23 @@ def _wide(mode):
     return sc.problem(10.0, th_dist=64, check_orientation=0)
 
 
+def _reordered(pr, order):
+    """the searched side's features in another order: new feature j is old feature order[j] (pr is changed in place and returned)"""
+    t = pr["train"]
+    for k in ("x", "y", "octave", "angle", "occupied", "desc"):
+        t[k] = np.ascontiguousarray(t[k][order])
+    t["cell_off"], t["cell_idx"] = matcher.build_grid(t["x"], t["y"], *GRID)
+    return pr
+
+
+def _limit(mode, seed, **kw):
+    """8191 searched features, the documented limit, and 3000 points; the features in a random order, so that the matches (_main puts
+    the features it projects from first) fall on both sides of index 4096: every bit of the candidate key's 13-bit index and every word
+    of ks_resolve's 8192-bit bitmap"""
+    pr = _main(mode, seed, nf=8191, nq=3000, **kw)
+    return _reordered(pr, np.random.RandomState(seed + 1).permutation(8191))
+
+
 def _over():
     """three problems, the second with 8192 features: it alone fails"""
     big = _main(0, 81, nf=8192, nq=20)
@@ -386,6 +403,7 @@ KF_BUILDERS = {
     "edge_0": lambda: _edge(0), "edge_1": lambda: _edge(1), "edge_2": lambda: _edge(2),
     "rot13": lambda: _main(2, 15, nf=500, nq=500, spread=True, th_dist=100),
     "wide_0": lambda: _wide(0), "wide_2": lambda: _wide(2),
+    "limit_0": lambda: _limit(0, 16), "limit_2": lambda: _limit(2, 17, th_dist=100),
     "empty_nq_0": lambda: _empty(0, "nq"), "empty_nq_1": lambda: _empty(1, "nq"), "empty_n_2": lambda: _empty(2, "n"), "empty_n_1": lambda: _empty(1, "n"),
 }
 KF_BUILDERS.update({"batch_%02d" % k: (lambda k=k: _main(k % 3, 100 + k, nf=90 + 17 * k, nq=70 + 13 * k, th=(10.0, 4.0, 10.0)[k % 3]))

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import bow_cases
+import parity_checks
 import bow_second_opinion as so
 from pointslot_amd import bow, keyframes
 from pointslot_amd.matcher import ORBmatcher
@@ -31,15 +32,7 @@ def _device_vocabulary(name):
     return _VOCABS[name]
 
 
-def _check_transform(got, ref, n, what=""):
-    word, node, ids, vals = ref
-    assert not got["failed"]
-    assert np.array_equal(got["word"], word), (what, np.argwhere(got["word"] != word)[:5].ravel())
-    assert np.array_equal(got["node"], node), (what, np.argwhere(got["node"] != node)[:5].ravel())
-    assert len(got["bow_id"]) == len(ids) and np.array_equal(got["bow_id"], ids), what
-    if len(ids):
-        rel = np.abs(got["bow_val"] - vals) / np.abs(vals)
-        assert rel.max() <= bow_cases.bow_val_bound(n), (what, rel.max(), bow_cases.bow_val_bound(n))
+_check_transform = parity_checks.check_transform
 
 
 @pytest.mark.parametrize("weighting", [so.TF_IDF, so.TF, so.IDF, so.BINARY])
@@ -128,6 +121,15 @@ def test_transform_beyond_the_limit_fails_alone(matcher):
     with pytest.raises(Exception) as e:
         voc.transform([big], 0, matcher=matcher)
     assert e.value.code == -3
+    # ... and a frame AT the limit on a 10^4-word tree, value for value, beside one beyond it
+    name = "limit_k10_L4"
+    feats = bow_cases.transform_features(name)
+    ref = bow_cases.transform_reference(name, 2)
+    assert len(feats) == bow.MAX_N == 8191 and len(ref[2]) > 4096
+    res = _device_vocabulary(name).transform([feats, np.concatenate([feats, feats[:1]]), feats[:100]], 2, matcher=matcher, partial_ok=True)
+    assert res[1]["failed"]
+    _check_transform(res[0], ref, len(feats), name)
+    _check_transform(res[2], bow_cases.second_opinion_vocabulary(name).transform(feats[:100], 2), 100, name)
 
 
 # ---- search ----------------------------------------------------------------------------------------------------------------

@@ -9,27 +9,14 @@ import pytest
 
 import kfdb_cases as kc
 import kfdb_second_opinion as so
+import parity_checks
 
 pytestmark = pytest.mark.gpu
 
 F32 = np.float32
 
 
-def _play(db, case):
-    from pointslot_amd import kfdb
-    out = []
-    for op in case["ops"]:
-        if op[0] == "add":
-            assert all(db.add(op[1], [case["kfs"][i] for i in op[1]]))
-        elif op[0] == "erase":
-            db.erase(op[1])
-        elif op[0] == "clear":
-            db.clear()
-        else:
-            res = db.query([dict(bow=q["bow"], mode=q["mode"], excluded=q["connected"]) for q in op[1]])
-            for q, r in zip(op[1], res):
-                out.append(dict(r, candidates=kfdb.select(q["mode"], q["min_score"], r, case["neigh"])))
-    return out
+_play = parity_checks.play_kfdb_device
 
 
 @functools.lru_cache(maxsize=None)
@@ -40,12 +27,7 @@ def _device(name):
     return _play(db, case), db
 
 
-def _same(got, want, where):
-    assert [int(x) for x in got["share_id"]] == [int(x) for x in want["share_id"]], where
-    assert np.array_equal(got["share_words"], want["share_words"]), where
-    assert got["share_score"].dtype == F32 and got["share_score"].tobytes() == want["share_score"].tobytes(), where
-    assert got["min_common_words"] == want["min_common_words"], where
-    assert got["candidates"] == want["candidates"], where
+_same = parity_checks.check_kfdb_query
 
 
 @pytest.mark.parametrize("name", ["hand", "a", "b", "batch", "batch_split"])
@@ -55,6 +37,17 @@ def test_query_equals_the_second_opinion(name):
     assert len(got) == len(want)
     for g, w in zip(got, want):
         _same(g, w, (name, w["query"]["qid"]))
+
+
+def test_vectors_at_the_word_limit():
+    """a stored vector and a query of 8191 words: the sharing lists, the scores of both modes and ps_kfdb_score"""
+    got, _ = _device("limit")
+    want = kc.second_opinion("limit")
+    assert len(got) == len(want) == 3 and len(want[0]["share_id"]) == 5 and (want[0]["share_score"] > 0).sum() >= 2
+    for g, w in zip(got[:2], want[:2]):
+        _same(g, w, ("limit", w["query"]["qid"]))
+    assert (want[2]["scores"] > 0).all()
+    parity_checks.check_kfdb_score(got[2]["scores"], want[2]["scores"], "limit")
 
 
 def test_hand_case_as_written():

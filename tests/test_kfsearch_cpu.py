@@ -11,6 +11,7 @@ import pytest
 
 import kfsearch_cases as kc
 import kfsearch_second_opinion as so
+import sweep_cases
 
 F32 = np.float32
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -109,14 +110,8 @@ def test_input_condition_of_the_gpu_comparison(name):
     correctly working implementations cannot disagree on a level.  No query is excluded."""
     ref = kc.reference(name)
     lv = ref["logv"][np.isfinite(ref["logv"])]
-    ratio = ref["ratio"][np.isfinite(ref["logv"])]
     assert np.isfinite(ref["logv"]).sum() == sum(g in ("empty", "nomatch", "match") for g in ref["gate"])
-    clamp = lambda v: np.clip(np.ceil(v), 0, 7)
-    step = 4 * np.spacing(np.abs(lv))
-    assert np.array_equal(clamp(lv - step), clamp(lv + step))
-    powers = np.array([1.2 ** k for k in range(-60, 61)])
-    gap = np.abs(ratio.astype(np.float64)[:, None] - powers[None, :]).min(axis=1) if len(ratio) else np.zeros(0)
-    assert (gap > 4 * np.spacing(ratio).astype(np.float64)).all()
+    assert sweep_cases.level_violations(ref) == (0, len(lv))       # the predicate itself: one statement, shared with the sweeps
 
 
 def test_decomposition_helpers_state_their_model():

@@ -6,13 +6,13 @@ import numpy as np
 import pytest
 
 import kfsearch_cases as kc
+import parity_checks
 from pointslot_amd import _lib
 from pointslot_amd.frame import DeviceFrame
 from pointslot_amd.matcher import ORBmatcher
 
 pytestmark = pytest.mark.gpu
-KF_KEYS = {0: ("match_of_train",), 1: ("best_idx", "best_dist"), 2: ("match_of_train",)}
-SIM3_KEYS = ("match12", "match1", "match2")
+KF_KEYS, SIM3_KEYS = parity_checks.KF_KEYS, parity_checks.SIM3_KEYS
 
 
 @pytest.fixture(scope="module")
@@ -22,16 +22,7 @@ def matcher():
     m.close()
 
 
-def _check_kf(got, ref, mode, what=""):
-    for key in KF_KEYS[mode]:
-        assert np.array_equal(got[key], ref[key]), (what, key, np.argwhere(got[key] != ref[key])[:5].ravel(), got[key][got[key] != ref[key]][:5], ref[key][got[key] != ref[key]][:5])
-    assert got["nmatches"] == ref["nmatches"], (what, got["nmatches"], ref["nmatches"])
-
-
-def _check_sim3(got, ref, what=""):
-    for key in SIM3_KEYS:
-        assert np.array_equal(got[key], ref[key]), (what, key, np.argwhere(got[key] != ref[key])[:5].ravel())
-    assert got["nfound"] == ref["nfound"], (what, got["nfound"], ref["nfound"])
+_check_kf, _check_sim3 = parity_checks.check_kf, parity_checks.check_sim3
 
 
 def _run(matcher, name):
@@ -42,6 +33,15 @@ def _run(matcher, name):
 def test_members_equal_the_second_opinion(matcher, name):
     pr, ref = kc.problem(name), kc.reference(name)
     assert ref["nmatches"] > 50
+    _check_kf(_run(matcher, name), ref, pr["mode"], name)
+
+
+@pytest.mark.parametrize("name", ["limit_0", "limit_2"])
+def test_searched_side_at_the_feature_limit(matcher, name):
+    """8191 searched features in a random order and 3000 points: matches at indices on both sides of 4096"""
+    pr, ref = kc.problem(name), kc.reference(name)
+    at = np.flatnonzero(ref["match_of_train"] >= 0)
+    assert len(pr["train"]["x"]) == 8191 and (at >= 4096).sum() > 200 and (at < 4096).sum() > 200
     _check_kf(_run(matcher, name), ref, pr["mode"], name)
 
 

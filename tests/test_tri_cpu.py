@@ -7,6 +7,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import sweep_cases
 import tri_cases
 import tri_second_opinion as so
 
@@ -118,7 +119,7 @@ def test_seeded_cases_are_well_posed(name):
     stable (its verdict survives +-1 float32 ulp on x3D and on the stereo cosine) and has sigma1 / sigma3 <= 1e5, so that two
     FP64 computations of the null vector agree far inside a float32 ulp.  No pair is left out of the GPU comparison."""
     ref = tri_cases.reference(name)
-    bad = [p for p in ref["pairs"] if not p["stable"] or (p["kind"] == "svd" and not p["ratio"] <= 1e5)]
+    bad = sweep_cases.tri_bad_pairs(ref)           # not stable, or svd with sigma1 / sigma3 > 1e5: one statement, shared with the sweeps
     assert not bad, bad[:5]
 
 

@@ -5,6 +5,7 @@ bit-equal where it comes from KeyFrame::UnprojectStereo."""
 import numpy as np
 import pytest
 
+import parity_checks
 import tri_cases
 import tri_second_opinion as so
 from pointslot_amd import _lib, keyframes
@@ -23,35 +24,7 @@ def matcher():
     m.close()
 
 
-def _ulps(a, b):
-    """distance in float32 steps (both finite, same sign or zero)"""
-    ia, ib = a.astype(F32).view(np.int32).astype(np.int64), b.astype(F32).view(np.int32).astype(np.int64)
-    ia = np.where(ia < 0, -(ia & 0x7FFFFFFF), ia); ib = np.where(ib < 0, -(ib & 0x7FFFFFFF), ib)
-    return np.abs(ia - ib)
-
-
-def _check(got, ref, what=""):
-    assert np.array_equal(got["match"], ref["match"]), (what, np.argwhere(got["match"] != ref["match"])[:5])
-    assert np.array_equal(got["nmatches"], ref["nmatches"]), (what, got["nmatches"], ref["nmatches"])
-    assert got["nnew"] == ref["nnew"], (what, got["nnew"], ref["nnew"])
-    if "status" not in ref:
-        assert "status" not in got
-        return
-    diff = np.argwhere(got["status"] != ref["status"])
-    assert not len(diff), (what, [(tuple(d), so_name(got["status"][tuple(d)]), so_name(ref["status"][tuple(d)])) for d in diff[:5]])
-    for p in ref["pairs"]:
-        if p["kind"] == "none" or p["status"] == so.W_ZERO or ref["match"][p["i"], p["idx1"]] < 0:
-            continue
-        g, r = got["x3d"][p["i"], p["idx1"]], ref["x3d"][p["i"], p["idx1"]]
-        if p["kind"] == "svd":
-            assert _ulps(g, r).max() <= 1, (what, p, g, r)
-        else:
-            assert np.array_equal(g.view(np.uint32), r.view(np.uint32)), (what, p, g, r)
-
-
-def so_name(code):
-    from pointslot_amd.matcher import TRI_STATUS
-    return TRI_STATUS[int(code)] if int(code) < len(TRI_STATUS) else int(code)
+_ulps, _check, so_name = parity_checks.ulps, parity_checks.check_tri, parity_checks.tri_status_name
 
 
 def _run(matcher, name):
@@ -169,16 +142,25 @@ def test_keyframe_1_from_a_frame_handle(matcher):
 
 def test_capacity_fails_that_problem_alone(matcher):
     big = keyframes.keyframe_set(41, n_kf=2, sizes=[8192, 40], flip_bits=0)
-    ok = keyframes.keyframe_set(42, n_kf=2, sizes=[8191, 40], flip_bits=0)
+    ok = tri_cases.problem("limit_8191x40")              # keyframe_set(42, n_kf=2, sizes=[8191, 40], flip_bits=0), as before
     small = tri_cases.problem("batch_1")
     with pytest.raises(_lib.PointslotError) as e:
         matcher.CreateNewMapPoints([keyframes.problem_of(big), small])
     assert e.value.code == _lib.PS_ERR_CAPACITY
-    got = matcher.CreateNewMapPoints([keyframes.problem_of(big), small, keyframes.problem_of(ok)], partial_ok=True)
+    got = matcher.CreateNewMapPoints([keyframes.problem_of(big), small, ok], partial_ok=True)
     assert got[0]["failed"] and not got[1]["failed"] and not got[2]["failed"]
     _check(got[1], tri_cases.reference("batch_1"), "beside a problem beyond the limits")
     assert got[2]["match"].shape == (1, 8191) and got[2]["nnew"] >= 0
+    _check(got[2], tri_cases.reference("limit_8191x40"), "8191 features beside a problem beyond the limits")
     too_many = keyframes.tri_problem(43, k=33, n1=8, n2=8)
     with pytest.raises(_lib.PointslotError) as e:
         matcher.CreateNewMapPoints([too_many])
     assert e.value.code == _lib.PS_ERR_CAPACITY
+
+
+def test_keyframes_at_the_feature_limit(matcher):
+    """8191 x 8191 features, one neighbour, 200 nodes: 32 workgroups in y, every word of the occupied bitmap, 32 trips of the
+    256-wide loops, matches on both sides of index 4096"""
+    ref = tri_cases.reference("limit_8191x8191")
+    assert (np.flatnonzero(ref["match"][0] >= 0) >= 4096).sum() > 100 and (ref["match"][0] >= 4096).sum() > 100 and ref["nnew"] > 100
+    _check(_run(matcher, "limit_8191x8191"), ref, "limit_8191x8191")

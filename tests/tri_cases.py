@@ -111,6 +111,9 @@ BUILDERS = {
     "batch_2": lambda: _sizes(33, 257, [64, 65, 1, 300, 129]),
     "batch_3": lambda: _sizes(34, 1, [300, 300]),
     "batch_4": lambda: _sizes(35, 199, [211, 0, 97, 5]),
+    # the documented limit of 8191 features: 32 workgroups in y, 256 words of the occupied bitmap, 32 trips of the `i += 256` loops
+    "limit_8191x40": lambda: keyframes.problem_of(keyframes.keyframe_set(42, n_kf=2, sizes=[8191, 40], flip_bits=0)),
+    "limit_8191x8191": lambda: keyframes.tri_problem(44, k=1, n1=8191, n2=8191, n_nodes=200),
 }
 BATCH = ("batch_0", "batch_1", "batch_2", "batch_3", "batch_4")
 
