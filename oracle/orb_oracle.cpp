@@ -1062,7 +1062,7 @@ static int stereo_match_keys(Extractor& EL, Extractor& ER, const KeyPoint* KL, c
       float bestuR = EL.mvScaleFactor[kpL.octave] * ((float)scaleduR0 + (float)bestincR + deltaR);
       float disparity = (uL - bestuR);
       if (disparity >= minD && disparity < maxD) {
-        if (disparity <= 0) { disparity = 0.01f; bestuR = uL - 0.01f; }
+        if (disparity <= 0) { disparity = 0.01; bestuR = uL - 0.01; }   // double literals, as in the reference: the subtraction is in double
         depth[iL] = mbf / disparity;
         u_right[iL] = bestuR;
         vDistIdx.push_back(std::pair<int, int>(bestDistS, iL));

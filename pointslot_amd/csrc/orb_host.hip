@@ -312,6 +312,14 @@ int build_plan(ps_orb* h, int w, int hgt) {
   PS_HIP(hipMalloc(&h->d_kept, (size_t)B * 4));
   PS_HIP(hipMalloc(&h->d_pairs, (size_t)B * sizeof(StPair)));
   PS_HIP(hipMalloc(&h->d_stscratch, (size_t)B * PS_ST_SCRATCH));
+  if (const char* fill = getenv("PS_DEBUG_FILL")) {   // diagnostic: the stereo matcher's buffers too; on the handle's stream, which is waited for below
+    const int v = atoi(fill);
+    PS_HIP(hipMemsetAsync(h->d_uright, v, (size_t)B * P.kp_cap * 4, h->stream));
+    PS_HIP(hipMemsetAsync(h->d_depth, v, (size_t)B * P.kp_cap * 4, h->stream));
+    PS_HIP(hipMemsetAsync(h->d_sad, v, (size_t)B * P.kp_cap * 4, h->stream));
+    PS_HIP(hipMemsetAsync(h->d_kept, v, (size_t)B * 4, h->stream));
+    PS_HIP(hipMemsetAsync(h->d_stscratch, v, (size_t)B * PS_ST_SCRATCH, h->stream));
+  }
   PS_HIP(hipMemsetAsync(h->d_counts, 0, (size_t)B * 4, h->stream));
   PS_HIP(hipStreamSynchronize(h->stream));
   h->planned = true;
@@ -922,6 +930,8 @@ int ps_orb_stereo_match_keys(ps_orb* left, ps_orb* right, const ps_keypoint* kps
   if (!left->d_objkeys) {
     PS_HIP(hipMalloc(&left->d_objkeys, total));
     PS_HIP(hipHostMalloc(&left->h_objkeys, total));
+    if (const char* fill = getenv("PS_DEBUG_FILL"))    // diagnostic: ordered before the upload below, on the same stream
+      PS_HIP(hipMemsetAsync(left->d_objkeys, atoi(fill), total, left->stream));
   }
   uint8_t* hb = left->h_objkeys; uint8_t* db = left->d_objkeys;
   memcpy(hb + o_kl, kps_l, (size_t)n_left * 28);

@@ -429,15 +429,23 @@ def _popcount_rows(a, b):
     return np.unpackbits(a ^ b, axis=-1).sum(-1)
 
 
-def stereo_matches(kps_l, desc_l, kps_r, desc_r, pyr_l, pyr_r, scale, inv_scale, mb, mbf):
+def stereo_matches(kps_l, desc_l, kps_r, desc_r, pyr_l, pyr_r, scale, inv_scale, mb, mbf, border=0, counts=None):
     """Frame::ComputeStereoMatches (/root/reference/src/Frame.cc:2142-2316) read off the reference: the row table of the right keypoints,
     best Hamming distance inside the disparity range and one octave, the 11 x 11 L1 slide over +-5 columns with `int bestDist` receiving
     the float SAD, the parabola, the disparity clamp (in DOUBLE where the reference subtracts the literal 0.01), the 1.5f * 1.4f * median cut.
-    kps: structured arrays with x, y, octave.  pyr: the (unpadded) level images."""
+    kps: structured arrays with x, y, octave.  pyr: the (unpadded) level images; with border = b the planes carry b more pixels on
+    every side (OracleORB.padded(l) with b = EDGE) and are read at an offset, so that a patch next to the image border reads the
+    plane's border as the reference's Mat does, where a slice of the unpadded level would wrap around.  counts: a dict that receives
+    how often every exit of the loop was taken (tests/stereo_cases.py: gate_counts); neither changes the arithmetic."""
     f = np.float32
+    b = int(border)
+
+    def hit(name, k=1):
+        if counts is not None:
+            counts[name] = counts.get(name, 0) + k
     n = len(kps_l)
     u_right = np.full(n, -1.0, f); depth = np.full(n, -1.0, f)
-    n_rows = pyr_l[0].shape[0]
+    n_rows = pyr_l[0].shape[0] - 2 * b
     rows = [[] for _ in range(n_rows)]
     for ir in range(len(kps_r)):
         ky = f(kps_r["y"][ir]); r = f(f(2.0) * f(scale[int(kps_r["octave"][ir])]))
@@ -453,9 +461,11 @@ def stereo_matches(kps_l, desc_l, kps_r, desc_r, pyr_l, pyr_r, scale, inv_scale,
         ul, vl, lev = f(kps_l["x"][il]), f(kps_l["y"][il]), int(kps_l["octave"][il])
         cand = np.asarray(rows[int(vl)], np.int64)
         if len(cand) == 0:
+            hit("empty_row")
             continue
         min_u, max_u = f(ul - max_d), f(ul - min_d)
         if max_u < 0:
+            hit("max_u_negative")
             continue
         ok = (octr[cand] >= lev - 1) & (octr[cand] <= lev + 1) & (xr[cand] >= min_u) & (xr[cand] <= max_u)
         cand = cand[ok]
@@ -465,7 +475,11 @@ def stereo_matches(kps_l, desc_l, kps_r, desc_r, pyr_l, pyr_r, scale, inv_scale,
             k = int(np.argmin(d))                                       # the first smallest: `dist < bestDist` keeps the earliest
             if d[k] < best_dist:
                 best_dist, best_r = int(d[k]), int(cand[k])
+                if int((d == d[k]).sum()) > 1:
+                    hit("tie")
+        hit("win_74", int(best_dist == th_orb - 1)); hit("loss_75", int(best_dist == th_orb))
         if best_dist >= th_orb:
+            hit("hamming")
             continue
         ur0 = xr[best_r]
         sf = f(inv_scale[lev])
@@ -476,14 +490,16 @@ def stereo_matches(kps_l, desc_l, kps_r, desc_r, pyr_l, pyr_r, scale, inv_scale,
         il_img, ir_img = pyr_l[lev], pyr_r[lev]
         cy, cxl = int(sv_l), int(su_l)
         iniu, endu = f(su_r0 + L - w), f(su_r0 + L + w + 1)
-        if iniu < 0 or endu >= ir_img.shape[1]:
+        if iniu < 0 or endu >= ir_img.shape[1] - 2 * b:
+            hit("iniu" if iniu < 0 else "endu")
             continue
+        cy, cxl = cy + b, cxl + b
         pl = il_img[cy - w:cy + w + 1, cxl - w:cxl + w + 1].astype(f)
         pl = pl - pl[w, w]
         best_s, best_inc = 2 ** 31 - 1, 0
         dists = np.zeros(2 * L + 1, f)
         for inc in range(-L, L + 1):
-            cxr = int(f(su_r0 + inc))
+            cxr = int(f(su_r0 + inc)) + b
             pr = ir_img[cy - w:cy + w + 1, cxr - w:cxr + w + 1].astype(f)
             pr = pr - pr[w, w]
             dist = f(np.abs(pl - pr).astype(np.float64).sum())           # cv::norm accumulates in double; the values are integers
@@ -491,31 +507,41 @@ def stereo_matches(kps_l, desc_l, kps_r, desc_r, pyr_l, pyr_r, scale, inv_scale,
                 best_s, best_inc = int(dist), inc
             dists[L + inc] = dist
         if best_inc == -L or best_inc == L:
+            hit("sad_edge")
             continue
         d1, d2, d3 = dists[L + best_inc - 1], dists[L + best_inc], dists[L + best_inc + 1]
         with np.errstate(divide="ignore", invalid="ignore"):
             delta = f(f(d1 - d3) / f(f(2.0) * f(f(d1 + d3) - f(f(2.0) * d2))))
         if not (delta >= -1 and delta <= 1):                              # (a NaN parabola passes `deltaR<-1 || deltaR>1` in C++ ...)
             if not np.isnan(delta):
+                hit("delta")
                 continue
+            hit("nan_parabola")
         best_ur = f(f(scale[lev]) * f(f(su_r0 + f(best_inc)) + delta))
         disparity = f(ul - best_ur)
         if disparity >= min_d and disparity < max_d:                      # (... and fails here)
             if disparity <= 0:
+                hit("zero_clamp")
                 disparity = f(0.01)
                 best_ur = f(np.float64(ul) - 0.01)
             depth[il] = f(f(mbf) / disparity); u_right[il] = best_ur
             dist_idx.append((best_s, il))
+        else:
+            hit("negative" if not disparity >= min_d else "beyond_max_d")
+    hit("accepted", len(dist_idx))
     if not dist_idx:
         return 0, u_right, depth
     dist_idx.sort()
     median = f(dist_idx[len(dist_idx) // 2][0])
+    if counts is not None:
+        counts["median"] = int(median)
     th = f(f(f(1.5) * f(1.4)) * median)
     kept = len(dist_idx)
     for s, il in reversed(dist_idx):
         if s < th:
             break
         u_right[il] = -1; depth[il] = -1; kept -= 1
+    hit("median_cut", len(dist_idx) - kept)
     return kept, u_right, depth
 
 

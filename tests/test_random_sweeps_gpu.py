@@ -3,7 +3,9 @@ parameters, masks, matcher scenes and optimiser graphs against the CPU checker, 
 budget each (a few seconds), so that every GPU test run also covers shapes no hand-written case has (tile / cell / tap edge cases of the
 extraction kernels in particular).  The tools exit non-zero on the first difference.  The sweeps of the mapping and place-recognition
 calls (tests/sweep_cases.py; tests/test_sweep_cases_cpu.py checks their input conditions and what they reach under these very seeds)
-run a second time with every fresh device buffer filled with 0xFF bytes: their scratch comes from the matcher's arena."""
+run a second time with every fresh device buffer filled with 0xFF bytes: their scratch comes from the matcher's arena.  So does the
+sweep of the stereo matcher (tests/stereo_cases.py, tests/test_stereo_cases_cpu.py): its result, SAD and row-bucket buffers and the
+key sets' staging buffer are poisoned with the pyramid arena."""
 import os
 import subprocess
 import sys
@@ -28,6 +30,7 @@ SWEEPS = [
     ("stress_bow.py", _committed("bow"), "0 mismatches"),                     # ComputeBoW and SearchByBoW in turn on one handle
     ("stress_kfdb.py", _committed("kfdb"), "0 mismatches"),                   # KeyFrameDatabase scripts: add / erase / clear / query / score
     ("stress_kfsearch.py", _committed("kfsearch"), "0 mismatches"),           # loop-closure / relocalisation projections and SearchBySim3
+    ("stress_stereo.py", _committed("stereo"), "0 mismatches"),               # ComputeStereoMatches (two handles, batch) and ComputeObjStereoMatches
 ]
 POISONED = SWEEPS[4:]
 
