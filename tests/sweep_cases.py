@@ -20,7 +20,8 @@ F32 = np.float32
 I32 = np.int32
 # the seed and the budget tests/test_random_sweeps_gpu.py runs each tool with; tests/test_sweep_cases_cpu.py checks these very runs
 COMMITTED = {"tri": (20250601, 60), "bow": (20250602, 20), "kfdb": (20250603, 60), "kfsearch": (20250604, 45),
-             "stereo": (20250605, 26)}                                    # (the stereo matcher's scenes: tests/stereo_cases.py)
+             "stereo": (20250605, 26),                                    # (the stereo matcher's scenes: tests/stereo_cases.py)
+             "match": (20250606, 39)}                                     # (the tracking thread's matchers: tests/match_cases.py)
 
 TRI_N1 = (1, 63, 64, 65, 255, 256, 257, 513, 1100)
 TRI_N2 = (1, 63, 64, 65, 130, 257, 600)

@@ -92,69 +92,8 @@ def test_dynamic_static_reprojection_test_equals_the_restatement():
 
 
 # ---- the search half of ORBmatcher::Fuse(ObjectKeyFrame*, points, th)   /root/reference/src/ORBmatcher.cc:1138-1260 -----------------------------
-def _fuse(pr, accumulate="double"):
-    """-> (best_idx, best_dist) per candidate point.  Every float of the reference a numpy float32; `Rco * Poj + tco` by either reading of
-    the cv::Mat expression (tests/match_second_opinion.py); cv::norm and Mat::dot accumulate in double; GetMin / MaxDistanceInvariance apply 0.8f / 1.2f."""
-    import math
-    import match_second_opinion as ms
-    F32 = np.float32
-    T, q = pr["train"], pr["query"]
-    g = ms.Grid(T["x"], T["y"], T["grid"])
-    tx, ty, toct, tur, tdesc = np.asarray(T["x"], F32), np.asarray(T["y"], F32), np.asarray(T["octave"]), np.asarray(T["u_right"], F32), np.asarray(T["desc"], np.uint8).reshape(-1, 32)
-    fx, fy, cx, cy, bf = [F32(v) for v in pr["K5"]]
-    R, t, ow = np.asarray(pr["R"], F32), np.asarray(pr["t"], F32), np.asarray(pr["ow"], F32)
-    Tm = np.zeros((3, 4), F32); Tm[:, :3] = R; Tm[:, 3] = t
-    b = [float(v) for v in pr["bounds"]]
-    sf, is2 = np.asarray(pr["scale_factors"], F32), np.asarray(pr["inv_level_sigma2"], F32)
-    logsf, nlev, th = F32(pr["log_scale_factor"]), int(pr["n_levels"]), F32(pr["th"])
-    m = len(q["valid"])
-    bi, bd = np.full(m, -1, np.int32), np.full(m, 256, np.int32)
-    for i in range(m):
-        if not q["valid"][i]:
-            continue
-        P = np.asarray(q["pos"][i], F32)
-        pc = ms._mat3_vec_plus(Tm, P, accumulate)
-        if pc[2] < 0:
-            continue
-        invz = F32(F32(1) / pc[2])
-        x, y = F32(pc[0] * invz), F32(pc[1] * invz)
-        u, v = F32(F32(fx * x) + cx), F32(F32(fy * y) + cy)
-        ur = F32(u - F32(bf * invz))
-        if not (float(u) >= b[0] and float(u) < b[1] and float(v) >= b[2] and float(v) < b[3]):
-            continue
-        po = [F32(P[c] - ow[c]) for c in range(3)]
-        dist = F32(math.sqrt(sum(float(c) * float(c) for c in po)))
-        if dist < F32(F32(0.8) * F32(q["min_dist"][i])) or dist > F32(F32(1.2) * F32(q["max_dist"][i])):
-            continue
-        n = np.asarray(q["normal"][i], F32)
-        if sum(float(po[c]) * float(n[c]) for c in range(3)) < 0.5 * float(dist):
-            continue
-        ratio = F32(F32(q["max_dist"][i]) / dist)
-        lvl = int(math.ceil(math.log(float(ratio)) / float(logsf)))
-        lvl = 0 if lvl < 0 else min(lvl, nlev - 1)
-        radius = F32(th * sf[lvl])
-        best, bidx = 256, -1
-        for j in g.features_in_area(u, v, radius, toct):
-            kl = int(toct[j])
-            if kl < lvl - 1 or kl > lvl:
-                continue
-            ex, ey = F32(u - tx[j]), F32(v - ty[j])
-            if tur[j] >= 0:
-                er = F32(ur - tur[j])
-                e2 = F32(F32(F32(ex * ex) + F32(ey * ey)) + F32(er * er))
-                if float(F32(e2 * is2[kl])) > 7.8:
-                    continue
-            else:
-                e2 = F32(F32(ex * ex) + F32(ey * ey))
-                if float(F32(e2 * is2[kl])) > 5.99:
-                    continue
-            d = ms.descriptor_distance(np.asarray(q["desc"][i], np.uint8), tdesc[j])
-            if d < best:
-                best, bidx = d, j
-        bd[i] = best
-        if best <= 50:
-            bi[i] = bidx
-    return bi, bd
+# (the restatement lives beside the other matchers' second opinions, where the sweep of tests/match_cases.py counts its gates)
+from match_second_opinion import fuse_search as _fuse
 
 
 def test_fuse_search_equals_the_restatement():

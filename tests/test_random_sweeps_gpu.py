@@ -5,7 +5,9 @@ extraction kernels in particular).  The tools exit non-zero on the first differe
 calls (tests/sweep_cases.py; tests/test_sweep_cases_cpu.py checks their input conditions and what they reach under these very seeds)
 run a second time with every fresh device buffer filled with 0xFF bytes: their scratch comes from the matcher's arena.  So does the
 sweep of the stereo matcher (tests/stereo_cases.py, tests/test_stereo_cases_cpu.py): its result, SAD and row-bucket buffers and the
-key sets' staging buffer are poisoned with the pyramid arena."""
+key sets' staging buffer are poisoned with the pyramid arena.  The committed scenes of the tracking thread's matchers
+(tests/match_cases.py, tests/test_match_cases_cpu.py; tools/stress_matchers.py --cases) run both ways as well: candidate keys, claim
+tables' backing store and the published frames all come from fresh device buffers."""
 import os
 import subprocess
 import sys
@@ -31,8 +33,15 @@ SWEEPS = [
     ("stress_kfdb.py", _committed("kfdb"), "0 mismatches"),                   # KeyFrameDatabase scripts: add / erase / clear / query / score
     ("stress_kfsearch.py", _committed("kfsearch"), "0 mismatches"),           # loop-closure / relocalisation projections and SearchBySim3
     ("stress_stereo.py", _committed("stereo"), "0 mismatches"),               # ComputeStereoMatches (two handles, batch) and ComputeObjStereoMatches
+    ("stress_matchers.py", ["--cases"] + _committed("match"), "0 mismatches"),   # the matchers' committed scenes, from host arrays and from frames
 ]
+# the second run, on poisoned device memory: every sweep of committed scenes (tri, bow, kfdb, kfsearch, stereo and the matchers' cases)
 POISONED = SWEEPS[4:]
+assert [s[0] for s in POISONED] == ["stress_tri.py", "stress_bow.py", "stress_kfdb.py", "stress_kfsearch.py", "stress_stereo.py", "stress_matchers.py"]
+
+
+def _ids(sweeps):
+    return [s[0][:-3] + ("_cases" if s[1][:1] == ["--cases"] else "") for s in sweeps]
 
 
 def _sweep(tool, args, expect, env=None):
@@ -43,12 +52,12 @@ def _sweep(tool, args, expect, env=None):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("tool,args,expect", SWEEPS, ids=[s[0][:-3] for s in SWEEPS])
+@pytest.mark.parametrize("tool,args,expect", SWEEPS, ids=_ids(SWEEPS))
 def test_random_sweep(tool, args, expect):
     _sweep(tool, args, expect)
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("tool,args,expect", POISONED, ids=[s[0][:-3] for s in POISONED])
+@pytest.mark.parametrize("tool,args,expect", POISONED, ids=_ids(POISONED))
 def test_random_sweep_with_poisoned_device_memory(tool, args, expect):
     _sweep(tool, args, expect, dict(os.environ, PS_DEBUG_FILL="255"))

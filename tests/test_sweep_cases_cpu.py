@@ -20,8 +20,10 @@ def _sweep(family):
 def test_the_gpu_suite_runs_the_committed_seeds():
     import test_random_sweeps_gpu as t
     for family, (seed, budget) in sc.COMMITTED.items():
+        # (the matchers' committed scenes are the --cases mode of the tool that also keeps its older random scenes)
+        tool, mode = ("stress_matchers.py", ["--cases"]) if family == "match" else ("stress_%s.py" % family, [])
         for rows in (t.SWEEPS, t.POISONED):                       # once plain, once with poisoned device memory
-            assert [s[1] for s in rows if s[0] == "stress_%s.py" % family] == [[str(seed), str(budget)]], family
+            assert [s[1] for s in rows if s[0] == tool and (not mode or s[1][:1] == mode)] == [mode + [str(seed), str(budget)]], family
 
 
 def test_same_seed_same_bytes():

@@ -7,7 +7,7 @@ for i in $(seq 0 $((N - 1))); do
   seed=$((S0 + i))
   for job in "stress_orb.py $seed 120" "stress_cvorb_batch.py $seed 16" "stress_matchers.py $seed" "stress_opt.py $seed" \
              "stress_tri.py $seed 120" "stress_bow.py $seed 30" "stress_kfdb.py $seed 60" "stress_kfsearch.py $seed 60" \
-             "stress_stereo.py $seed 40"; do
+             "stress_stereo.py $seed 40" "stress_matchers.py --cases $seed"; do
     out=$(timeout 900 python tools/$job 2>&1); rc=$?
     echo "$job rc=$rc: $(echo "$out" | tail -1 | cut -c1-160)"
     if [ $rc -ne 0 ]; then fail=$((fail + 1)); echo "$out" | tail -30; fi
