@@ -13,7 +13,7 @@
 #include "dyn_plan.h"
 
 extern "C" void psk_pose_lm_launch(const PoProb*, int, const PoVertex*, const float*, const float*, const float*,
-                                   const uint8_t*, uint8_t*, double*, uint8_t*, void*, double*, int32_t*, double*, hipStream_t);
+                                   const uint8_t*, uint8_t*, double*, uint8_t*, void*, double*, int32_t*, double*, int, int, hipStream_t);
 
 struct BaCtx { uint8_t* d_buf = nullptr; size_t d_bytes = 0; uint8_t* h_buf = nullptr; size_t h_bytes = 0; };
 
@@ -29,6 +29,7 @@ struct ps_optimizer {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   float last_kernel_ms = 0;
   bool trace = false;
+  int pose_waves = 0;               // PS_POSE_WAVES at creation: 1 / 4 forces pose_lm's form, 0 leaves it to the launcher's rule
   std::vector<double> last_trace;   // [nprob][PS_PO_TRACE][3]
 };
 
@@ -120,7 +121,7 @@ int run_pose_only(ps_optimizer* m, const std::vector<PoView>& pv, std::vector<Se
   psk_pose_lm_launch((const PoProb*)(D + o_prob), nprob, (const PoVertex*)(D + o_vert), (const float*)(D + o_x),
                      (const float*)(D + o_obs), (const float*)(D + o_is2), D + o_val, D + o_out, (double*)(D + o_chi),
                      D + o_st, D + o_ce, (double*)(D + o_pose), (int32_t*)(D + o_res), m->trace ? (double*)(D + o_tr) : nullptr,
-                     m->stream);
+                     pv[0].mode, m->pose_waves, m->stream);
   PS_HIP(hipGetLastError());
   PS_HIP(hipEventRecord(m->ev1, m->stream));
   PS_HIP(hipMemcpyAsync(H + o_out, D + o_out, io_end - o_out, hipMemcpyDeviceToHost, m->stream));
@@ -152,6 +153,7 @@ int ps_optimizer_create(int device, ps_optimizer** out) {
   PS_HIP(hipSetDevice(device));
   ps_optimizer* m = new ps_optimizer();
   m->device = device;
+  if (const char* pw = getenv("PS_POSE_WAVES")) { const int w = atoi(pw); m->pose_waves = (w == 1 || w == 4) ? w : 0; }
   hipError_t e = hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking);
   if (e != hipSuccess) { delete m; return ps_set_error(PS_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e)); }
   hipEventCreate(&m->ev0);

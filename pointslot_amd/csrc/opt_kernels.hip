@@ -6,6 +6,8 @@
 // between rounds — without a host round trip.  A problem has k SE3 vertices (k = 1 for PoseOptimization,
 // k = number of objects for CFSE3: g2o solves them as ONE graph, i.e. one shared lambda / gain ratio /
 // stop rule and a block-diagonal 6k x 6k system), each with its own contiguous range of unary edges.
+// The workgroup is four waves (a launch of few problems: one problem done soonest) or one wave (a launch
+// of two or more problems per CU: eight problems per CU instead of two); see pose_lm<NW> and psk_pose_lm_waves.
 //
 // Per LM iteration every thread evaluates its edges (error, analytic 2x6/3x6 Jacobian, Huber weight),
 // keeps 21 + 6 + 1 FP64 partial sums in registers (upper triangle of J^T W J, J^T W e, robust chi2),
@@ -20,6 +22,7 @@
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include <stdint.h>
+#include <atomic>
 #include "opt_plan.h"
 #include "se3.h"
 
@@ -31,12 +34,14 @@ namespace {
 #ifndef PO_JMAX
 #define PO_JMAX 9      // damping trials whose solves are done side by side once a first trial was rejected (g2o stops after 10 trials: 1 + 9)
 #endif
-static_assert(PO_T % 64 == 0, "only whole waves may leave the kernel early (see NT below)");
+static_assert(PO_T == 256, "the widest form is four waves per problem");
 
+// NW = waves per problem (the workgroup is 64 NW threads): the buffers the waves meet in are sized by it
+template <int NW>
 struct PoShared {
-  double red[PO_T / 64][28];
+  double red[NW][28];
   double out[28];
-  double outg[PO_T / 64][28];       // group_sum: the sums of the vertices worked on side by side
+  double outg[NW][28];       // group_sum: the sums of the vertices worked on side by side
   double chiv[PS_PO_MAX_K];         // robust chi2 per vertex of the last linearisation
   double pose[PS_PO_MAX_K][7];      // current estimates
   double pose0[PS_PO_MAX_K][7];     // estimates at entry (PoseOptimization restarts every round from them)
@@ -49,9 +54,9 @@ struct PoShared {
   double prior_err[PS_PO_MAX_K][3];
   uint8_t prior_robust[PS_PO_MAX_K];
   int icount;
-  double red1[2][PO_T / 64];        // block_sum1: the waves' partial sums, two buffers used in turn
+  double red1[2][NW];        // block_sum1: the waves' partial sums, two buffers used in turn
   int nv[PS_PO_MAX_K];              // valid edges per vertex = the length of its compacted edge list
-  int wcnt[PO_T / 64];              // compaction: valid slots in each wave's share of a vertex's range
+  int wcnt[NW];              // compaction: valid slots in each wave's share of a vertex's range
 };
 
 __device__ __forceinline__ double shfl_xor_d(double v, int m) {
@@ -59,6 +64,19 @@ __device__ __forceinline__ double shfl_xor_d(double v, int m) {
   lo = __shfl_xor(lo, m);
   hi = __shfl_xor(hi, m);
   return __hiloint2double(hi, lo);
+}
+
+// The workgroup's meeting point.  A one-wave workgroup has nobody to wait for: its lanes only have to see each other's LDS and
+// global writes, which the wave-level fence gives without an s_barrier.
+template <int NW>
+__device__ __forceinline__ void po_sync() {
+  if (NW == 1) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  } else {
+    __syncthreads();
+  }
 }
 
 // One value-halving step of the reductions below between the lanes l and l ^ 32 (W = 32) or l ^ 16 (W = 16): the lower lane of a pair keeps a and
@@ -78,8 +96,9 @@ __device__ __forceinline__ double swap_add_d(double a, double b) {
 }
 
 // sums acc[0..N) over the workgroup in a fixed order; the result lands in s.out[0..N) for every thread
-template <int N>
-__device__ void block_sum(double* acc, PoShared& s, int nthr) {
+// (one wave per problem: the in-wave half is the whole sum and goes straight to s.out)
+template <int N, int NW>
+__device__ void block_sum(double* acc, PoShared<NW>& s, int nthr) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (N > 4) {
     // Many values: instead of one 6-step butterfly per value (6 N exchanges), every step halves the number of values a lane
@@ -106,7 +125,12 @@ __device__ void block_sum(double* acc, PoShared& s, int nthr) {
       }
     }
     const double total = v[0] + shfl_xor_d(v[0], 1);
-    __syncthreads();   // protect s.out / s.red from the previous use
+    po_sync<NW>();   // protect s.out / s.red from the previous use
+    if (NW == 1) {
+      if ((lane & 1) == 0 && (lane >> 1) < N) s.out[lane >> 1] = total;
+      po_sync<NW>();
+      return;
+    }
     if ((lane & 1) == 0 && (lane >> 1) < N) s.red[wave][lane >> 1] = total;
   } else {
 #pragma unroll
@@ -116,19 +140,19 @@ __device__ void block_sum(double* acc, PoShared& s, int nthr) {
       for (int d = 32; d >= 1; d >>= 1) v += shfl_xor_d(v, d);
       acc[i] = v;
     }
-    __syncthreads();   // protect s.out / s.red from the previous use
+    po_sync<NW>();   // protect s.out / s.red from the previous use
     if (lane == 0)
 #pragma unroll
       for (int i = 0; i < N; i++) s.red[wave][i] = acc[i];
   }
-  __syncthreads();
+  po_sync<NW>();
   if (threadIdx.x < N) {
     double v = 0;
 #pragma unroll
     for (int w = 0; w < nthr / 64; w++) v += s.red[w][threadIdx.x];
     s.out[threadIdx.x] = v;
   }
-  __syncthreads();
+  po_sync<NW>();
 }
 
 // ONE value summed over the workgroup, returned to every thread (r05: the damping trials end in this reduction - 25 to 50 of them per
@@ -168,13 +192,16 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   }
   return v;
 }
-__device__ __forceinline__ double block_sum1(double v, PoShared& s, int nthr, int& turn) {
+// (one wave per problem: the butterfly leaves the sum on every lane; the fence stands in for the barrier the callers rely on)
+template <int NW>
+__device__ __forceinline__ double block_sum1(double v, PoShared<NW>& s, int nthr, int& turn) {
   v = wave_sum_d(v);
+  if (NW == 1) { po_sync<NW>(); return v; }
   if ((threadIdx.x & 63) == 0) s.red1[turn][threadIdx.x >> 6] = v;
   __syncthreads();
   double t = 0;
 #pragma unroll
-  for (int w = 0; w < PO_T / 64; w++) if (w < nthr / 64) t += s.red1[turn][w];
+  for (int w = 0; w < NW; w++) if (w < nthr / 64) t += s.red1[turn][w];
   turn ^= 1;
   return t;
 }
@@ -182,8 +209,8 @@ __device__ __forceinline__ double block_sum1(double v, PoShared& s, int nthr, in
 // The same reduction per GROUP of waves: the workgroup is split into G = 1, 2 or 4 groups of PO_T / G threads that work on different
 // vertices of a CFSE3 graph at the same time (g = the thread's group, tg its index inside it); sums land in s.outg[g][0..N).
 // With G = 1 this is block_sum: same order of additions.
-template <int N>
-__device__ void group_sum(double* acc, PoShared& s, int G, int g, int tg, int nthr) {
+template <int N, int NW>
+__device__ void group_sum(double* acc, PoShared<NW>& s, int G, int g, int tg, int nthr) {
   static_assert(N > 4 && N <= 32, "group_sum: 5 .. 32 values");
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   double v[32];
@@ -285,23 +312,29 @@ __device__ __forceinline__ PoEdge po_load(const float4* cedge, const uint8_t* st
 #ifndef PO_OCC_ATTR
 #define PO_OCC_ATTR      // developer knob (tools/build_variant.sh): e.g. __attribute__((amdgpu_waves_per_eu(3,3))) - 222 registers give two workgroups per
 #endif                   // CU; capped to 168 / 128 the kernel spills and the headline loses 2 % (r04)
-__global__ __launch_bounds__(PO_T) PO_OCC_ATTR void pose_lm(const PoProb* probs, const PoVertex* verts, const float* xw,
+// NW waves per problem.  Four waves finish ONE problem soonest and serve the launches of a few problems; at 222 registers a SIMD holds two waves,
+// a CU two four-wave problems, and a launch of more problems than that runs in rounds while every resident wave issues on about a sixth of its
+// cycles (dependent FP64 chains, barriers around the reductions, three waves waiting for wave 0's solves).  Narrow forms trade a problem's latency
+// for residency: with NW = 1 a CU holds eight problems, every barrier is a wave-level fence, the cross-wave stage of the reductions is gone and
+// nobody waits for the solve.  psk_pose_lm_launch picks the form per launch.  Within one form the order of every sum is fixed.
+template <int NW>
+__global__ __launch_bounds__(64 * NW) PO_OCC_ATTR void pose_lm(const PoProb* probs, const PoVertex* verts, const float* xw,
                                                 const float* obs, const float* inv_sigma2, const uint8_t* valid,
                                                 uint8_t* outlier, double* chi2c, uint8_t* state, float4* cedge, double* poses,
                                                 int32_t* results, double* trace) {
-  __shared__ PoShared s;
+  __shared__ PoShared<NW> s;
   POP_DECL;
   const PoProb P = probs[blockIdx.x];
   const int tid = threadIdx.x;
   const int k = P.k;
-  // A CFSE3 graph of one or two objects - a few hundred edges - runs on 128 of the workgroup's threads: the other two waves leave here
+  // A CFSE3 graph of one or two objects - a few hundred edges - runs on 128 of the four-wave workgroup's threads: the other two waves leave here
   // (a barrier only counts the waves that are still alive).  With fewer lanes the reductions and the barriers between the short edge
   // passes weigh less (0.84 -> 0.70 ms per step in the tracker, r04); graphs of more objects keep all four waves (up to four objects
-  // are linearised side by side, one per wave), PoseOptimization its 256 lanes for a frame's ~1000 edges.
-  const int NT = (P.mode == 1 && k <= 2) ? 128 : PO_T;
+  // are linearised side by side, one per wave), PoseOptimization its 256 lanes for a frame's ~1000 edges.  The narrow forms keep all their waves.
+  const int NT = NW == 4 ? ((P.mode == 1 && k <= 2) ? 128 : 256) : 64 * NW;
   if (tid >= NT) return;
-  // CFSE3 graphs: G vertices are linearised side by side, each by a group of GT threads (whole waves)
-  const int G = min(k >= 4 ? 4 : (k >= 2 ? 2 : 1), NT / 64), GT = NT / G, g = tid / GT, tg = tid - g * GT;
+  // CFSE3 graphs: G vertices are linearised side by side, each by a group of GT threads (whole waves); one wave takes them one after the other
+  const int G = NW == 1 ? 1 : min(k >= 4 ? 4 : (k >= 2 ? 2 : 1), NT / 64), GT = NT / G, g = tid / GT, tg = tid - g * GT;
   const double deltaMono = (double)(float)sqrt(5.991), deltaStereo = (double)(float)sqrt(7.815);
   double* tr = trace ? trace + (size_t)blockIdx.x * PS_PO_TRACE * 3 : nullptr;
   int ntr = 0;
@@ -329,18 +362,20 @@ __global__ __launch_bounds__(PO_T) PO_OCC_ATTR void pose_lm(const PoProb* probs,
       const int n = V.e_end - V.e_begin;
       const int per = (((n + nw - 1) / nw) + 63) & ~63;
       const int wb = V.e_begin + wave * per, we = min(wb + per, V.e_end);
-      int c = 0;
-      for (int i0 = wb; i0 < we; i0 += 512) {
-        uint8_t f[8];
-#pragma unroll
-        for (int u = 0; u < 8; u++) { const int i = i0 + u * 64 + lane; f[u] = i < we ? valid[i] : (uint8_t)0; }
-#pragma unroll
-        for (int u = 0; u < 8; u++) c += __popcll(__ballot(f[u] != 0));
-      }
-      if (lane == 0) s.wcnt[wave] = c;
-      __syncthreads();
       int run = V.e_begin, tot = 0;
-      for (int w = 0; w < nw; w++) { const int cw = s.wcnt[w]; if (w < wave) run += cw; tot += cw; }
+      if (NW > 1) {
+        int c = 0;
+        for (int i0 = wb; i0 < we; i0 += 512) {
+          uint8_t f[8];
+#pragma unroll
+          for (int u = 0; u < 8; u++) { const int i = i0 + u * 64 + lane; f[u] = i < we ? valid[i] : (uint8_t)0; }
+#pragma unroll
+          for (int u = 0; u < 8; u++) c += __popcll(__ballot(f[u] != 0));
+        }
+        if (lane == 0) s.wcnt[wave] = c;
+        __syncthreads();
+        for (int w = 0; w < nw; w++) { const int cw = s.wcnt[w]; if (w < wave) run += cw; tot += cw; }
+      }                              // (one wave: it owns the whole range, its running prefix is the count)
       for (int i0 = wb; i0 < we; i0 += 256) {
         uint8_t f[4];
         float e[4][7];
@@ -368,9 +403,10 @@ __global__ __launch_bounds__(PO_T) PO_OCC_ATTR void pose_lm(const PoProb* probs,
           run += __popcll(bal);
         }
       }
+      if (NW == 1) tot = run - V.e_begin;
       if (tid == 0) s.nv[o] = tot;
       nInitial += tot;
-      __syncthreads();               // s.wcnt is free again; the records are visible to the whole workgroup
+      po_sync<NW>();                 // s.wcnt is free again; the records are visible to the whole workgroup
     }
   }
   const int nTotalEdges = nInitial + (P.mode == 1 ? k : 0);
@@ -387,9 +423,9 @@ __global__ __launch_bounds__(PO_T) PO_OCC_ATTR void pose_lm(const PoProb* probs,
 
   for (int it = 0; it < 4; it++) {
     if (P.mode == 0) {   // vSE3->setEstimate(Converter::toSE3Quat(pFrame->mTcw)) every round (Optimizer.cc:394)
-      __syncthreads();
+      po_sync<NW>();
       for (int i = tid; i < k * 7; i += NT) (&s.pose[0][0])[i] = (&s.pose0[0][0])[i];
-      __syncthreads();
+      po_sync<NW>();
     }
     // active set = level-0 edges; a vertex without active edges is not optimised
     int nact = 0;
@@ -514,9 +550,9 @@ __global__ __launch_bounds__(PO_T) PO_OCC_ATTR void pose_lm(const PoProb* probs,
             }
           }
         }
-        __syncthreads();
+        po_sync<NW>();
         for (int o = 0; o < k; o++) chi_total += s.chiv[o];      // in vertex order, as the sequential loop added them
-        __syncthreads();
+        po_sync<NW>();
         POP_MARK(1);
         double currentChi = chi_total;
         const double iniChi = currentChi;
@@ -545,7 +581,7 @@ __global__ __launch_bounds__(PO_T) PO_OCC_ATTR void pose_lm(const PoProb* probs,
           bool ok2 = true;
           double scale = 0;
           if (sp_i == sp_n) {
-            __syncthreads();      // everybody is done with the batch before (s.cpose / s.cx / s.out of the last trial)
+            po_sync<NW>();      // everybody is done with the batch before (s.cpose / s.cx / s.out of the last trial)
             const int J = qmax == 0 ? 1 : min(min(10 - qmax, PO_JMAX), 64 / k);
             if (tid < 64) {
               const int j = tid / k, o = tid - j * k;
@@ -639,7 +675,7 @@ __global__ __launch_bounds__(PO_T) PO_OCC_ATTR void pose_lm(const PoProb* probs,
               if (tid == 0) s.cok = okmask;
             }
             sp_n = J; sp_i = 0;
-            __syncthreads();
+            po_sync<NW>();
           }
           // the trial in turn: its estimate and increment stay where the batch left them (s.pose keeps the estimate the trials start from:
           // a rejected trial has nothing to restore)
@@ -703,9 +739,9 @@ __global__ __launch_bounds__(PO_T) PO_OCC_ATTR void pose_lm(const PoProb* probs,
             lambda *= fmax(1. / 3., alpha);
             ni = 2;
             currentChi = tempChi;
-            __syncthreads();
-            if (tid < k * 7) (&s.pose[0][0])[tid] = (&s.cpose[ci][0])[tid];       // the accepted estimate
-            __syncthreads();
+            po_sync<NW>();
+            for (int i = tid; i < k * 7; i += NT) (&s.pose[0][0])[i] = (&s.cpose[ci][0])[i];       // the accepted estimate (up to 112 doubles: more than one wave has lanes)
+            po_sync<NW>();
           } else {
             lambda *= ni;
             ni *= 2;
@@ -720,7 +756,7 @@ __global__ __launch_bounds__(PO_T) PO_OCC_ATTR void pose_lm(const PoProb* probs,
       }
     }
     // ---- chi-square classification (Optimizer.cc:404-466 / :652-725) ----
-    __syncthreads();
+    po_sync<NW>();
     POP_MARK(0);
     int bad = 0;
     for (int o = 0; o < k; o++) {
@@ -747,7 +783,7 @@ __global__ __launch_bounds__(PO_T) PO_OCC_ATTR void pose_lm(const PoProb* probs,
     nBadTotal = (int)block_sum1((double)bad, s, NT, turn);
     POP_MARK(4);
   }
-  __syncthreads();
+  po_sync<NW>();
   for (int i = tid; i < k * 7; i += NT) poses[(size_t)P.v_off * 7 + i] = (&s.pose[0][0])[i];
   if (tid == 0) {
     results[blockIdx.x] = P.mode == 0 ? nInitial - nBadTotal : 1;
@@ -756,13 +792,50 @@ __global__ __launch_bounds__(PO_T) PO_OCC_ATTR void pose_lm(const PoProb* probs,
   POP_PRINT();
 }
 
+// CUs of the current device, read once per device
+int po_cu_count() {
+  static std::atomic<int> cus[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+  int n = cus[dev].load(std::memory_order_relaxed);
+  if (n == 0) {
+    hipDeviceProp_t prop;
+    n = hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    cus[dev].store(n, std::memory_order_relaxed);
+  }
+  return n;
+}
+
 }  // namespace
+
+// The form the rule gives a launch of `nprob` problems of `mode` (0 PoseOptimization, 1 CFSE3) on the current device.
+// Four waves per problem below two problems per CU, one wave from there on, for both kinds of launch.  Two per CU (512 on 256 CUs) is what the
+// four-wave form holds at once, and while it does it owns the register file of every SIMD.  Measured (r07, profiles/r07_pose_waves_sweep.txt,
+// tracked frames/s, four waves -> one wave):
+//   256 problems per launch:   1 group 36.8 -> 34.2 k, 3 groups 48.6 -> 46.9 k      the wide form wins: a launch of one wave per CU is all latency
+//   512 problems per launch:   1 group 42.5 -> 41.2 k (-3 %), 2 groups 47.7 -> 47.9 k, 3 groups (the headline) 49.0 -> 50.3 k (+2.7 %)
+//   1024 / 1536 per launch:    1 group 44.2 -> 45.3 k / 45.2 -> 47.0 k (+2.5 % / +4 %)
+// A handle of exactly 512 sequences that has the chip to itself is the wide form's best case (one full round) and pays 3 %; as soon as
+// other handles' kernels run beside it, or the launch is larger, the narrow form wins.  Narrowing only the CFSE3 launches at 512 (a separate
+// threshold per mode) gave the headline 0.8 %, both 2.7 %; two waves per problem never won a row and is not built.
+extern "C" int psk_pose_lm_waves(int nprob, int mode) {
+  (void)mode;                                  // (the sweep found no reason for a threshold per mode)
+  return nprob >= 2 * po_cu_count() ? 1 : 4;
+}
 
 extern "C" void psk_pose_lm_launch(const PoProb* probs, int nprob, const PoVertex* verts, const float* xw,
                                    const float* obs, const float* inv_sigma2, const uint8_t* valid, uint8_t* outlier,
                                    double* chi2c, uint8_t* state, void* cedge, double* poses, int32_t* results, double* trace,
-                                   hipStream_t st) {
+                                   int mode, int waves, hipStream_t st) {
   // cedge: 32 bytes of scratch per edge slot (the compacted edge records), 16-byte aligned
-  hipLaunchKernelGGL(pose_lm, dim3(nprob), dim3(PO_T), 0, st, probs, verts, xw, obs, inv_sigma2, valid, outlier, chi2c,
-                     state, (float4*)cedge, poses, results, trace);
+  // mode: what the launch holds (0 PoseOptimization, 1 CFSE3 graphs); waves: 1 / 4 forces the form (a handle's PS_POSE_WAVES), anything
+  // else leaves it to the rule above.
+  int nw = waves;
+  if (nw != 1 && nw != 4) nw = psk_pose_lm_waves(nprob, mode);
+  if (nw == 1)
+    hipLaunchKernelGGL(pose_lm<1>, dim3(nprob), dim3(64), 0, st, probs, verts, xw, obs, inv_sigma2, valid, outlier, chi2c,
+                       state, (float4*)cedge, poses, results, trace);
+  else
+    hipLaunchKernelGGL(pose_lm<4>, dim3(nprob), dim3(PO_T), 0, st, probs, verts, xw, obs, inv_sigma2, valid, outlier, chi2c,
+                       state, (float4*)cedge, poses, results, trace);
 }

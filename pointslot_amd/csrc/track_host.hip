@@ -21,7 +21,7 @@ const OrbPlan* psi_orb_plan(ps_orb*);
 int psi_orb_prepare(ps_orb*, int, int);
 void psk_pj_launch(const PjArrays*, int, int, int, int, int, hipStream_t);
 void psk_pose_lm_launch(const PoProb*, int, const PoVertex*, const float*, const float*, const float*, const uint8_t*, uint8_t*,
-                        double*, uint8_t*, void*, double*, int32_t*, double*, hipStream_t);
+                        double*, uint8_t*, void*, double*, int32_t*, double*, int, int, hipStream_t);
 void psk_trk_begin(const TrkArrays*, int, hipStream_t);
 void psk_trk_after_mm1(const TrkArrays*, hipStream_t);
 void psk_trk_after_mm(const TrkArrays*, int, hipStream_t);
@@ -65,6 +65,7 @@ struct ps_tracker {
   PjArrays pj_mm1, pj_mm2, pj_lm;
   // pose optimiser work arrays
   double* po_chi2 = nullptr; uint8_t* po_state = nullptr; float* po_cedge = nullptr;   // cedge: pose_lm's compacted edge records, 32 B per slot
+  int pose_waves = 0;            // PS_POSE_WAVES at creation: 1 / 4 forces pose_lm's form, 0 leaves it to the launcher's rule
   int32_t* d_overflow = nullptr;
   int step = 0;
   float mb = 0, mbf = 0;
@@ -300,13 +301,13 @@ int queue_chain(ps_tracker* t, const uint8_t* d_imgs, int stride, size_t image_p
   psk_pj_launch(&t->pj_mm2, S, cap, cap, 1, 0, st); mark(TS_SEARCH);   // the 2 * th retry; empty problems where it is not needed
   psk_trk_after_mm(A, t->step, st); mark(TS_GLUE);
   psk_pose_lm_launch(A->po_prob, S, A->po_vert, A->cur.xw, A->po_obs, A->po_is2, A->cur.mp_valid, A->cur.outlier, t->po_chi2, t->po_state,
-                     t->po_cedge, A->po_pose, A->po_result, nullptr, st);
+                     t->po_cedge, A->po_pose, A->po_result, nullptr, 0, t->pose_waves, st);
   mark(TS_POSE);
   psk_trk_after_pose1(A, t->step, st); mark(TS_GLUE);
   psk_pj_launch(&t->pj_lm, S, cap, cap, 0, 0, st); mark(TS_SEARCH);
   psk_trk_after_lm(A, st); mark(TS_GLUE);
   psk_pose_lm_launch(A->po_prob, S, A->po_vert, A->cur.xw, A->po_obs, A->po_is2, A->cur.mp_valid, A->cur.outlier, t->po_chi2, t->po_state,
-                     t->po_cedge, A->po_pose, A->po_result, nullptr, st);
+                     t->po_cedge, A->po_pose, A->po_result, nullptr, 0, t->pose_waves, st);
   mark(TS_POSE);
   psk_trk_finish(A, t->step, st);
   psk_trk_stamp_overflow(A, t->d_overflow, t->step, st); mark(TS_GLUE);
@@ -329,13 +330,13 @@ int queue_chain(ps_tracker* t, const uint8_t* d_imgs, int stride, size_t image_p
     mark(TS_OBJ_BRUTEFORCE);
     psk_ob_after_bf(O, t->step, st); mark(TS_OBJ_GLUE);
     psk_pose_lm_launch(O->po_prob, S, O->po_vert, O->cur.mp_po, O->po_obs, O->po_is2, O->cur.mp_valid, O->cur.outlier, t->ob_chi2, t->ob_state,
-                       t->ob_cedge, O->po_pose, O->po_result, nullptr, st);
+                       t->ob_cedge, O->po_pose, O->po_result, nullptr, 1, t->pose_waves, st);
     mark(TS_OBJ_CFSE3);
     psk_ob_after_cf1(O, t->step, st); mark(TS_OBJ_GLUE);
     psk_pj_launch(&t->pj_obj, S * K, O->LC, O->OC, 0, 0, st); mark(TS_OBJ_SEARCH);
     psk_ob_after_lm(O, t->step, st); mark(TS_OBJ_GLUE);
     psk_pose_lm_launch(O->po_prob, S, O->po_vert, O->cur.mp_po, O->po_obs, O->po_is2, O->cur.mp_valid, O->cur.outlier, t->ob_chi2, t->ob_state,
-                       t->ob_cedge, O->po_pose, O->po_result, nullptr, st);
+                       t->ob_cedge, O->po_pose, O->po_result, nullptr, 1, t->pose_waves, st);
     mark(TS_OBJ_CFSE3);
     psk_ob_finish(O, t->step, st); mark(TS_OBJ_GLUE);
   }
@@ -364,6 +365,7 @@ int ps_tracker_create(const ps_tracker_config* cfg, ps_tracker** out) {
   ps_tracker* t = new ps_tracker();
   t->cfg = *cfg;
   t->orb = orb;
+  if (const char* pw = getenv("PS_POSE_WAVES")) { const int w = atoi(pw); t->pose_waves = (w == 1 || w == 4) ? w : 0; }
   t->stream = psi_orb_stream(orb);   // the extractor's stream: its kernels and the chain behind them are ordered without events
   TrkArrays& A = t->A;
   memset(&A, 0, sizeof(A));
