@@ -576,6 +576,50 @@ int ps_search_by_sim3(ps_matcher* m, ps_sim3_problem* probs, int nprob);
 int ps_search_by_sim3_frames(ps_matcher* m, ps_sim3_problem* probs, ps_frame* const* frames1, ps_frame* const* frames2, int nprob);
 
 /* ------------------------------------------------------------------------------------------------
+ * Sim3Solver (src/Sim3Solver.cc) - the RANSAC over Horn's closed-form similarity between the two keyframes of a loop candidate.
+ * One call evaluates every hypothesis of every problem of a batch; a problem is one candidate keyframe pair.  The call keeps no
+ * state between invocations and is exact given the draws: what iterate() does sequentially (:141-208) is a walk over `inliers`.
+ *   n, x3dc1 / x3dc2 [n][3] : mvX3Dc1 / mvX3Dc2, the matched points in the frame of camera 1 / 2 (:95-99)
+ *   max_err1 / max_err2 [n] : mvnMaxError1 / 2 as floats.  They are std::vector<size_t> in the reference: 9.210 * sigma2 is
+ *                             TRUNCATED to an integer before the float comparison (level 1 gates at 13, not 13.26)
+ *   k1 / k2                 : fx, fy, cx, cy of keyframe 1 / 2
+ *   fix_scale               : mbFixScale
+ *   nhyp, draws [nhyp][3]   : per hypothesis the three raw rand() values (0 .. 2^31 - 1) its draw consumes.  Hypothesis h applies
+ *                             DUtils::Random::RandomInt to them and draws without replacement from 0 .. n - 1 as :164-178 do
+ *   min_inliers             : mRansacMinInliers
+ *   inliers [nhyp]          : out, mnInliersi of every hypothesis
+ *   model [nhyp][13]        : out, ms12i, mR12i row-major, mt12i.  A quaternion with a zero imaginary part gives NaN, as in the
+ *                             reference (0 * (1 / 0)): the hypothesis has no inliers
+ *   mask                    : out or NULL, nhyp x ceil(n / 64) words: bit (i & 63) of word (i >> 6) is mvbInliersi[i]
+ *   first_success           : out, the smallest h with inliers[h] > min_inliers, else -1
+ *   best                    : out, the last h that attains the running maximum (:184 compares with >=), -1 without hypotheses
+ * Arithmetic: the float expressions as written; cv::Mat products, Mat::dot and cv::norm with products and sums in double, rounded
+ * once; the eigenvector is that of the float32 N, computed in FP64, with q0 >= 0 (DESIGN.md 4j lists the readings).
+ * Limits: n <= 32767, nhyp <= 4096; a problem beyond them fails alone (first_success = best = -2) and the call returns
+ * PS_ERR_CAPACITY after the others are served.  A problem with nhyp == 0, n < min_inliers or n < 3 is legal, costs nothing and
+ * leaves its arrays untouched (first_success = best = -1).  ps_matcher_last_kernel_ms covers the call. */
+typedef struct ps_sim3_ransac_problem {
+  int32_t n;
+  const float* x3dc1;
+  const float* x3dc2;
+  const float* max_err1;
+  const float* max_err2;
+  float k1[4], k2[4];
+  int32_t fix_scale;
+  int32_t nhyp;
+  const int32_t* draws;
+  int32_t min_inliers;
+  int32_t* inliers;
+  float* model;
+  uint64_t* mask;
+  int32_t first_success;
+  int32_t best;
+} ps_sim3_ransac_problem;
+int ps_sim3_ransac(ps_matcher* m, ps_sim3_ransac_problem* probs, int nprob);
+/* Sim3Solver::SetRansacParameters (:115-139), host only: *iterations = mRansacMaxIts for n correspondences, with the float epsilon. */
+int ps_sim3_ransac_iterations(double probability, int min_inliers, int max_iterations, int n, int* iterations);
+
+/* ------------------------------------------------------------------------------------------------
  * Bag of words - the DBoW2 vocabulary the reference keeps as ORBVocabulary (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h with
  * FORB), Frame::ComputeBoW / KeyFrame::ComputeBoW (src/Frame.cc:2040-2047, src/KeyFrame.cc:114-123) and the two
  * ORBmatcher::SearchByBoW overloads (src/ORBmatcher.cc:280-410, :646-781).
